@@ -12,10 +12,20 @@ trivially (independent series, zero exchange — SURVEY.md §8e): each rank
 owns nseries/N series, weak scaling, no data-path collective; value is the
 whole-job aggregate.
 
-cpu_baseline: the oracle (C restatement of the reference decoder; the only
-permitted oracle use in this file) timed on host cores over a bounded sample
-of the same streams. roofline: HIP-event kernel timing of the dominant
-(decode) kernel vs the 8 TB/s HBM3E peak.
+A plain run (--gpus 1 --steps N --warmup W) builds the batch, warms up,
+times the N steps and prints the result line; everything else is behind
+--full:
+
+cpu_baseline (--full only): the oracle (C restatement of the reference
+decoder; the only permitted oracle use in this file) timed on host cores over
+a bounded sample of the same streams. roofline: HIP-event kernel timing of
+the dominant (decode) kernel vs the 8 TB/s HBM3E peak (taken from the timed
+steps themselves, so it costs no run of its own).
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step
+returned to its caller as DIR/<name>.npy (float32/float64): a fixed, seeded
+sample of series, identified by their index in the generated workload, so
+two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -42,7 +52,7 @@ def shard_range(nseries, world, rank):
     return lo, hi
 
 
-def parse_args():
+def parse_args(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=10)
@@ -56,6 +66,12 @@ def parse_args():
     p.add_argument("--cpu-sample-series", type=int, default=0,
                    help="series in the cpu_baseline sample (0 = auto-size to ~15s)")
     p.add_argument("--skip-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: "
+                        "the cpu_baseline leg (oracle on the host cores)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last step's outputs "
+                        "(a fixed seeded sample of series) as DIR/<name>.npy")
     p.add_argument("--no-sort", action="store_true",
                    help="disable length-sorted wave scheduling")
     p.add_argument("--layout", choices=["index", "sorted"], default=None,
@@ -74,11 +90,11 @@ def parse_args():
                    default="decode",
                    help="decode = headline metric (BASELINE configs[1]); "
                         "encode/rollup = BASELINE configs[2]/[3]")
-    return p.parse_args()
+    return p.parse_args(argv)
 
 
-def main():
-    args = parse_args()
+def main(argv=None):
+    args = parse_args(argv)
     import torch
     import m3_amd
     from m3_amd import engine, workload
@@ -144,6 +160,7 @@ def main():
     # length-sorted wave scheduling: every wavefront decodes 64 similar-cost
     # streams (stream length is known before decode)
     d_perm = None
+    d_order = None  # output row i holds workload series d_order[i] (None: i)
     if not args.no_sort:
         d_perm = torch.argsort(d_lens).to(torch.int32)
     if args.layout is None:
@@ -169,6 +186,7 @@ def main():
         # that was at perm[i] before the repack
         if expected_counts is not None:
             expected_counts = expected_counts[d_perm.long()]
+        d_order = d_perm
         d_perm = None
 
     parse_only = args.mode == "parse-only"
@@ -247,8 +265,20 @@ def main():
         except Exception:
             pass
 
+    if rank == 0 and args.dump_outputs:
+        series, rows = sample_series(torch, n_local, 24 * args.npts + 16,
+                                     device, d_order)
+        arrays = {"counts": out_counts[rows], "errs": out_errs[rows]}
+        if not parse_only:
+            # a row is defined up to its count; the tail is never written
+            live = (torch.arange(args.npts, device=device)[None, :]
+                    < out_counts[rows][:, None])
+            arrays.update(split_ns("ts", out_ts[rows] * live),
+                          vals=torch.where(live, out_vals[rows], 0.0))
+        dump_outputs(args.dump_outputs, series, arrays)
+
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.skip_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.skip_cpu_baseline:
         cpu_baseline = run_cpu_baseline(args, d_blob, d_offsets, d_lens, n_local)
 
     if rank == 0:
@@ -291,6 +321,51 @@ def main():
 
     if dist:
         dist.destroy_process_group()
+
+
+DUMP_BUDGET_BYTES = 48 * 10**6  # all of --dump-outputs stays under 64 MB
+DUMP_MAX_SERIES = 4096
+
+
+def sample_series(torch, n_local, row_bytes, device, d_order=None, seed=0):
+    """Fixed seeded sample of workload series for --dump-outputs, sized so
+    that `row_bytes` dumped bytes per series stay within the budget.
+    Returns (series, rows): the sampled series' workload indices (sorted
+    numpy int64) and, as a device tensor, the output rows holding them
+    (d_order: output row i holds workload series d_order[i])."""
+    k = int(min(n_local, DUMP_MAX_SERIES, max(1, DUMP_BUDGET_BYTES // row_bytes)))
+    series = np.sort(np.random.default_rng(seed).choice(n_local, size=k,
+                                                        replace=False))
+    d_series = torch.from_numpy(series).to(device)
+    if d_order is None:
+        return series, d_series
+    inv = torch.empty(n_local, dtype=torch.int64, device=device)
+    inv[d_order.long()] = torch.arange(n_local, device=device)
+    return series, inv[d_series]
+
+
+def split_ns(name, d_ns):
+    """int64 ns timestamps do not fit a float64 mantissa: dump them as
+    <name>_sec + <name>_nsec, each exact in float64."""
+    ns = d_ns.cpu().numpy()
+    return {name + "_sec": ns // 10**9, name + "_nsec": ns % 10**9}
+
+
+def dump_outputs(outdir, series, arrays):
+    """Write DIR/<name>.npy: float64 for 8-byte element types, else float32
+    (both exact for the values written here)."""
+    os.makedirs(outdir, exist_ok=True)
+    arrays = dict(arrays, series=series)
+    total = 0
+    for name, a in arrays.items():
+        if hasattr(a, "cpu"):
+            a = a.cpu().numpy()
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype.itemsize == 8 else np.float32)
+        total += a.nbytes
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    print(f"[bench] dumped {len(arrays)} arrays ({total/1e6:.1f} MB, "
+          f"{len(series)} series) to {outdir}", flush=True)
 
 
 def run_cpu_baseline(args, d_blob, d_offsets, d_lens, n_local):
@@ -370,6 +445,12 @@ def bench_encode(args, torch, engine, workload, device, n_local, lo):
         step()
     torch.cuda.synchronize()
     dt = time.time() - t0
+    if args.dump_outputs:
+        series, rows = sample_series(torch, n_local, 4 * out_stride + 8,
+                                     device)
+        dump_outputs(args.dump_outputs, series,
+                     {"stream_bytes": d_out[rows], "lens": d_lens[rows],
+                      "errs": d_errs[rows]})
     npts_total = n_local * npts
     dps = npts_total * args.steps / dt
     algo = enc_bytes + 16 * npts_total
@@ -417,6 +498,13 @@ def bench_rollup(args, torch, engine, d_blob, d_offsets, d_lens, enc_bytes,
         step()
     torch.cuda.synchronize()
     dt = time.time() - t0
+    if args.dump_outputs:
+        series, rows = sample_series(torch, n_local,
+                                     nbuckets * (len(aggs) * 8 + 16) + 4,
+                                     device)
+        dump_outputs(args.dump_outputs, series,
+                     dict(split_ns("window_ts", wts[rows]), aggs=out[rows],
+                          errs=errs[rows]))
     npts_total = n_local * args.npts
     dps = npts_total * args.steps / dt
     algo = enc_bytes + n_local * nbuckets * (len(aggs) * 8 + 8)
@@ -483,9 +571,15 @@ def bench_tiles(args, torch, engine, d_blob, d_offsets, d_lens, enc_bytes,
     torch.cuda.synchronize()
     t0 = time.time()
     for _ in range(args.steps):
-        step()
+        tb, tl, tc = step()
     torch.cuda.synchronize()
     dt = time.time() - t0
+    if args.dump_outputs:
+        series, rows = sample_series(torch, n_local, 4 * tb.shape[1] + 8,
+                                     device)
+        dump_outputs(args.dump_outputs, series,
+                     {"tile_bytes": tb[rows], "tile_lens": tl[rows],
+                      "tile_counts": tc[rows]})
     npts_total = n_local * args.npts
     dps = npts_total * args.steps / dt
     print(json.dumps({
