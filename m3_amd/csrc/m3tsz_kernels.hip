@@ -6,21 +6,23 @@
  * cites per function; format: src/dbnode/encoding/m3tsz + aggregator
  * semantics), NOT a port of its Go code:
  *
- *  - One SERIES PER WAVEFRONT. M3TSZ is a sequentially-dependent
- *    variable-length code, so all 64 lanes run the (wave-uniform) bit parser
- *    redundantly — branches cost s_branch, not divergence — and the wave's
- *    parallelism is spent on the memory system:
- *      decode: lane (n & 63) captures point n in registers; every 64 points
- *        the wave stores 64x(8B ts + 8B val) contiguously — fully coalesced
- *        512B transactions. The compressed stream is read as aligned
- *        big-endian u64 words at one wave-uniform address (L1 broadcast).
- *      encode: lane (w & 63) captures output word w; every 64 words the wave
- *        stores 512B coalesced.
- *      rollup: bucket values are staged to LDS, quantiles picked by a
- *        rank-select over lanes (no sort network needed), reproducing the
- *        reference CKMS walk exactly (see ckms_small_n semantics below).
+ *  - Decode, encode and the lane-tier rollup run one SERIES PER LANE: M3TSZ
+ *    is a sequentially-dependent variable-length code, so each lane keeps
+ *    its own parser state in VGPRs and a wave works on 64 independent
+ *    streams; branches diverge only where the lanes disagree.
+ *      decode: each lane pulls its stream through a per-lane LDS word ring
+ *        (topped up by deferred global loads, see BitReader) and stages 8
+ *        decoded (ts, val) pairs in an LDS tile; the wave then flushes the
+ *        tile transposed, 8 consecutive 8B stores per output row segment,
+ *        which keeps write traffic at the algorithmic 16 B/pt.
+ *      encode: each lane emits completed 64-bit words into its own row.
+ *      rollup: the lane tier keeps per-bucket state in registers and small
+ *        quantile buckets in a per-lane sorted LDS row; deep buckets retry
+ *        on the wave-per-series tiers (k_rollup_batch, k_rollup_ckms),
+ *        which run ONE series per wavefront with a wave-uniform parser and
+ *        reproduce the reference CKMS walk exactly.
  *  - Streams are decoded from 8-byte-aligned offsets, zero-padded to an
- *    8-byte boundary (layout contract in m3gpu.h; pack_streams emits 16B
+ *    8-byte boundary (layout contract in m3gpu.h; pack_streams emits 64B
  *    alignment, which satisfies it) so every refill is an aligned u64 load.
  *  - Wave64 only; no CUDA shims, no hipified code.
  *
@@ -111,12 +113,11 @@ __device__ __forceinline__ double go_modf(double v, double* ip) {
 /* istream.go:73-115 over reader64.go:40-80, with the m3gpu.h layout
  * contract: stream starts 8B-aligned, buffer zero-padded to 8B. */
 
-/* Per-lane LDS input ring geometry (decode kernel): 8 buffered words per
- * lane (one 64B chunk = one HBM line), rows padded to 9 so that both the
- * per-lane ds_read_b64 pulls and the refill ds_write_b64 bursts are
- * bank-conflict-free (b64 reads bank on (a/4)%64 in 2x32 lane groups,
- * writes on (a/4)%32 in 4x16 groups; the 9-word row stride makes lane
- * bases land on distinct bank pairs). */
+/* Per-lane LDS input ring geometry (series-per-lane kernels): IN_WORDS
+ * buffered u64 words per lane, rows IN_STRIDE words apart (unpadded: 4
+ * words x 64 lanes x 4 waves = 8 KB/block, which together with the 32 KB
+ * output tile keeps 4 blocks/CU; an 8-word ring drops that to 3 and
+ * measured slower). IN_WORDS must be a power of two. */
 #ifndef IN_WORDS
 #define IN_WORDS 4
 #endif
@@ -124,6 +125,25 @@ __device__ __forceinline__ double go_modf(double v, double* ip) {
 #define IN_STRIDE 4
 #endif
 
+/* The ring pointer carries its address space in its type: a generic pointer
+ * here lets the optimizer merge the ring read with the underrun path's
+ * global load into one load through a selected pointer, i.e. a flat load. */
+typedef __attribute__((address_space(3))) uint64_t lds_u64;
+
+/* One tile's ring top-up in flight: raw (un-swapped) little-endian words
+ * exactly as the loads deliver them, plus how many of them are real. Lives
+ * in the tile loop's scope, NOT in the reader: nothing may read, copy or
+ * select these registers between refill_issue() and refill_commit(), or
+ * the compiler has to wait for the loads (vmcnt) right there. */
+struct RingPending {
+    uint64_t w[IN_WORDS];
+    uint32_t n;
+};
+
+/* RING is a compile-time property of the kernel: true for the
+ * series-per-lane kernels (k_decode_batch, k_rollup_lane), false for the
+ * wave-per-series rollup and CKMS kernels. */
+template <bool RING>
 struct BitReader {
     /* 128-bit register lookahead (`a` = next bits, `b` = following word,
      * both byte-swapped to stream bit order; `p` = bits of `a` already
@@ -135,16 +155,15 @@ struct BitReader {
      * word, so the window itself can always hold 128 physical bits.
      *
      * Words arrive one of two ways:
-     *  - LDS ring (decode kernel, `lds` set): refill() tops the per-lane
-     *    ring up to 16 words once per 8-point tile — each lane issues up
-     *    to 8 back-to-back loads of CONSECUTIVE words of its own stream,
-     *    so the per-lane 64B line is fetched once and consumed fully
-     *    (L1-amortized), and the long-latency global gathers leave the
-     *    per-point dependency chain entirely: the parser's word pulls are
-     *    cheap ds_read_b64s.
-     *  - direct (`lds` null, rollup/merge kernels): a 1-deep register
-     *    prefetch (`pfw`) beyond the window, i.e. 3 words of lookahead,
-     *    keeps the refill load issued ~128 bits before first use. */
+     *  - ring (RING): refill_issue()/refill_commit() top the per-lane
+     *    IN_WORDS-word LDS ring up once per 8-point tile with consecutive
+     *    words of the lane's own stream, so the long-latency global
+     *    gathers leave the per-point dependency chain: the parser's word
+     *    pulls are ds_read_b64s. A lane that drains its ring inside a
+     *    tile (dense streams) falls back to an in-chain global load.
+     *  - direct (!RING): a 1-deep register prefetch (`pfw`) beyond the
+     *    window, i.e. 3 words of lookahead, keeps the refill load issued
+     *    ~128 bits before first use. */
     const uint64_t* words;
     uint64_t a, b, c;   /* c: ring-word prefetch — the ds_read latency sits
                          * between one crossing and the NEXT, not in the
@@ -153,19 +172,17 @@ struct BitReader {
     int64_t bits_left;  /* un-consumed stream bits (from the true byte len) */
     uint32_t wnext;     /* next word index to pull into the window */
     uint32_t wtotal;    /* ceil(len/8) */
-    uint64_t* lds;      /* this lane's ring base, or nullptr */
-    uint32_t rfill;     /* words fetched into the ring so far */
-    uint64_t pend[IN_WORDS]; /* deferred refill: loads issued at tile start */
-    uint32_t pend_n;
+    lds_u64* lds;       /* ring mode: this lane's ring base */
+    uint32_t rfill;     /* ring mode: words fetched into the ring so far */
     uint64_t pfw;       /* direct mode: extra prefetched word */
 
     __device__ __forceinline__ uint64_t next_word() {
         uint64_t w;
-        if (lds) {
+        if constexpr (RING) {
             /* ring hit is the steady state (refill runs per tile); a
-             * mid-tile underrun (adversarially dense streams consuming
-             * >16 words in 8 points) falls back to a direct load —
-             * correct, just slower */
+             * mid-tile underrun (streams consuming more than the ring
+             * holds in 8 points) falls back to a direct load — correct,
+             * just slower, and its wait drains every store in flight */
             if (wnext < rfill) w = lds[wnext & (IN_WORDS - 1)];
             else w = (wnext < wtotal) ? __builtin_bswap64(words[wnext]) : 0;
         } else {
@@ -177,48 +194,70 @@ struct BitReader {
         return w;
     }
 
-    /* Deferred per-tile ring top-up, CHUNK-granular: one refill = the next
-     * whole 64B line of this lane's stream (8 consecutive u64 loads issued
-     * back-to-back — the first fetches the line, the rest hit L1 within
-     * the burst; with 64B-aligned stream packing every line is fetched
-     * exactly once, no inter-tile L1 retention needed). refill_issue()
-     * starts the loads at TILE START only when the whole ring is free;
-     * refill_commit() writes them to the ring at TILE END, after the
-     * tile's output stores have issued — gfx9 vmcnt retires in issue
-     * order, so the commit's counted wait isolates these loads and never
-     * drains the in-flight output stores. The loads' latency hides under
-     * the whole tile's parsing. */
+    /* Deferred ring top-up. refill_issue() runs at the start of a span of
+     * points with the whole wave converged and issues up to IN_WORDS global
+     * loads per lane back to back; refill_commit() byte-swaps them and
+     * writes them to the ring at the end of the span, before the tile's
+     * output stores issue. gfx9 vmcnt retires in issue order, so the
+     * commit's wait covers these loads and whatever was issued before them
+     * — the PREVIOUS tile's output stores, a whole tile old — and never
+     * the stores the flush is about to issue. The loads' latency hides
+     * under the span's parsing.
+     *
+     * What makes that hold in the compiled kernel: each load is
+     * exec-masked to the lanes that want word i (a lane reads words
+     * [rfill, rfill + n) of its own stream and nothing else), its
+     * destination is zeroed BEFORE the branch and is a value scoped to the
+     * span, not reader state carried round the loop — so there is no copy
+     * or select at the branch's join, nothing touches the register until
+     * the commit, and the compiler places no wait at the issue. */
 #ifndef RF_LOW
 #define RF_LOW 3 /* refill when <= this many ring words remain. Topping up
-                  * every tile (word-granular bursts, L1-amortized) measured
-                  * faster than whole-chunk-only refills (RF_LOW 0): the ring
-                  * then never dries mid-tile, so the parser's underrun
-                  * fallback (an in-chain global gather whose wait also
-                  * drains in-flight output stores) stays off the hot path */
+                  * word by word at every chance re-fetches each 64B line
+                  * several times (FETCH_SIZE ~5x the stream) but keeps the
+                  * ring from drying inside a span; whole-ring-only refills
+                  * (RF_LOW 0) were re-measured with the deferred refill in
+                  * place and still lose: 16.57 vs 16.11 ms */
 #endif
-    __device__ __forceinline__ void refill_issue(bool active) {
-        if (!lds) return;
+    __device__ __forceinline__ RingPending refill_issue(bool active) {
+        static_assert(RING, "ring mode only");
         if (rfill < wnext) rfill = wnext; /* resync: underrun consumed
                                            * [rfill, wnext) directly */
-        uint32_t used = rfill - wnext;
-        pend_n = 0;
-        if (active && used <= RF_LOW && rfill < wtotal) {
-            uint32_t n = wtotal - rfill;
-            uint32_t room = IN_WORDS - used;
-            if (n > room) n = room;
-            pend_n = n;
+        const uint32_t used = rfill - wnext;
+        uint32_t n = wtotal - rfill;
+        const uint32_t room = IN_WORDS - used;
+        if (n > room) n = room;
+        if (!(active && used <= RF_LOW && rfill < wtotal)) n = 0;
+        RingPending pd;
+        pd.n = n;
 #pragma unroll
-            for (uint32_t i = 0; i < IN_WORDS; i++)
-                if (i < pend_n) pend[i] = __builtin_bswap64(words[rfill + i]);
+        for (uint32_t i = 0; i < IN_WORDS; i++) {
+            pd.w[i] = 0;
+            if (i < n) pd.w[i] = words[rfill + i];
         }
+        return pd;
     }
-    __device__ __forceinline__ void refill_commit() {
-        if (!lds) return;
+    __device__ __forceinline__ void refill_commit(const RingPending& pd) {
+        static_assert(RING, "ring mode only");
+        /* The one place the burst is waited for, by the whole wave and for
+         * all IN_WORDS loads at once. The empty asm only pins that: it
+         * "uses" each raw word here, so (a) the compiler cannot fold the
+         * byte swap below back up into refill_issue() (it would wait for
+         * the loads right where they issue), and (b) no load is left
+         * pending past the commit when no lane wanted its word — the next
+         * tile's burst would then have to wait for it behind this tile's
+         * output stores. */
+        uint64_t w[IN_WORDS];
+#pragma unroll
+        for (uint32_t i = 0; i < IN_WORDS; i++) {
+            w[i] = pd.w[i];
+            asm volatile("" : "+v"(w[i]));
+        }
 #pragma unroll
         for (uint32_t i = 0; i < IN_WORDS; i++)
-            if (i < pend_n) lds[(rfill + i) & (IN_WORDS - 1)] = pend[i];
-        rfill += pend_n;
-        pend_n = 0;
+            if (i < pd.n)
+                lds[(rfill + i) & (IN_WORDS - 1)] = __builtin_bswap64(w[i]);
+        rfill += pd.n;
     }
 
     __device__ __forceinline__ void init(const uint8_t* base, uint64_t off,
@@ -226,13 +265,13 @@ struct BitReader {
         words = (const uint64_t*)(base + off);
         wtotal = (l + 7) >> 3;
         bits_left = (int64_t)l * 8;
-        lds = ring;
         wnext = 0;
-        rfill = 0;
-        pend_n = 0;
-        if (ring) {
-            refill_issue(true);
-            refill_commit();
+        if constexpr (RING) {
+            lds = (lds_u64*)ring;
+            rfill = 0;
+            /* called with the whole wave converged */
+            const RingPending pd = refill_issue(true);
+            refill_commit(pd);
         } else {
             pfw = wtotal ? __builtin_bswap64(words[0]) : 0;
         }
@@ -274,8 +313,9 @@ struct BitReader {
 /* Port of the reference decode state machine: iterator.go:47-219,
  * timestamp_iterator.go:41-361, float_encoder_iterator.go:105-165. */
 
-struct Decoder {
-    BitReader r;
+template <bool RING>
+struct DecoderT {
+    BitReader<RING> r;
     int64_t prev_time, prev_time_delta;
     int64_t unit_ns; /* cached UNIT_NS_D[time_unit] (0 when unit invalid) */
     double mult_pow;  /* cached 10^mult (mult changes rarely; keeping the
@@ -289,7 +329,16 @@ struct Decoder {
 
     __device__ __forceinline__ void set_unit(uint8_t tu) {
         time_unit = tu;
-        unit_ns = unit_valid(tu) ? UNIT_NS_D[tu] : 0;
+        /* Series-per-lane kernels (the wave-per-series ones keep this state
+         * in scalar registers, where the lookup is a scalar load):
+         * the per-lane table lookup is a global load. Pin its wait HERE,
+         * on this rare path (the empty asm "uses" the result): left to
+         * the compiler, the load stays in flight until the first use of
+         * unit_ns, which is in the per-point path, and the vmcnt(0) there
+         * drains the ring top-up and every output store in flight. */
+        int64_t ns = unit_valid(tu) ? UNIT_NS_D[tu] : 0;
+        if constexpr (RING) asm volatile("" : "+v"(ns));
+        unit_ns = ns;
     }
 
     /* optional annotation capture (m3gpu_decode_batch_dev_ann): events
@@ -302,6 +351,7 @@ struct Decoder {
     __device__ __forceinline__ void init(const uint8_t* base, uint64_t off, uint32_t len,
                          bool intopt, uint8_t dunit, uint64_t* ring = nullptr,
                          uint8_t* ann = nullptr, uint32_t ann_stride = 0) {
+        /* `ring` is this lane's LDS ring row (RING), ignored otherwise */
         r.init(base, off, len, ring);
         prev_time = 0; prev_time_delta = 0;
         int_val = 0; prev_float_bits = 0; prev_xor = 0;
@@ -874,6 +924,9 @@ struct Decoder {
     }
 };
 
+using Decoder = DecoderT<false>;     /* wave-per-series kernels: direct reader */
+using RingDecoder = DecoderT<true>;  /* series-per-lane kernels: LDS ring */
+
 /* ========================= decode kernel ========================= */
 /* ONE SERIES PER LANE: a wave decodes 64 independent streams in parallel,
  * one point per active lane per iteration. The VLC parser state lives in
@@ -881,19 +934,30 @@ struct Decoder {
  * (host-side batches group similar series for lane coherence, but any order
  * is correct).
  *
- * Memory structure (v6):
- *  - INPUT through a per-lane LDS ring (BitReader::refill): the global
- *    gathers leave the per-point chain — once per 8-point tile each lane
- *    bursts up to 8 loads of consecutive words of its own stream (per-lane
- *    64B lines fetched once, L1-amortized), and the parser pulls words
- *    with cheap conflict-free ds_read_b64s.
- *  - OUTPUT accumulated in per-lane REGISTERS (8 ts + 8 val slots, indexed
- *    by the unrolled tile counter) and flushed as 4+4 back-to-back 16B
- *    stores into the lane's own rows: consecutive stores complete each
- *    64B line, so write-combining holds WRITE_SIZE at the algorithmic
- *    16 B/pt with no LDS transpose and no cross-lane shuffles. */
+ * Memory structure:
+ *  - INPUT through a per-lane LDS ring (BitReader::refill_issue/_commit):
+ *    the global gathers leave the per-point chain — every RF_SPAN points
+ *    each lane issues up to IN_WORDS loads of consecutive words of its own
+ *    stream, commits them to its ring RF_SPAN points later, and the parser
+ *    pulls words with ds_read_b64s.
+ *  - OUTPUT staged in an LDS tile, [64 lanes][8 points] of (ts, val) pairs
+ *    with an XOR column swizzle — one ds_write_b128 per point — and flushed
+ *    every 8 points TRANSPOSED: lane l covers row (l>>3)+8j, point (l&7),
+ *    so 8 lanes write one row's 64 contiguous bytes per array and
+ *    WRITE_SIZE stays at the algorithmic 16 B/pt. */
 
 #define DEC_TILE 8
+/* points parsed between a ring top-up's issue and its commit; divides
+ * DEC_TILE. 2 = four top-ups per tile: the dense stream kinds consume 6-8
+ * words per 8 points, twice what the ring holds, and with one top-up per
+ * tile they spend half of every tile in the parser's in-chain underrun
+ * load, whose vmcnt(0) also drains the output stores. The span trades that
+ * against how long a load has to land before its commit waits for it.
+ * Same box, 1M x 1440 decode: span 8 16.1 ms, 4 15.9,
+ * 2 14.5, 1 15.3. */
+#ifndef RF_SPAN
+#define RF_SPAN 2
+#endif
 
 __global__ void __launch_bounds__(BLOCK_THREADS, 4) /* hold the 128-VGPR
     granule: ring + tiles = 40 KB/block -> 4 blocks/CU, 4 waves/SIMD */
@@ -923,7 +987,7 @@ k_decode_batch(const uint8_t* __restrict__ blobs,
     longlong2 (*tile)[DEC_TILE] = tile_all[wave];
 
     const bool in_range = slot < nseries;
-    Decoder d;
+    RingDecoder d;
     d.init(blobs, in_range ? offsets[series] : 0, in_range ? lens[series] : 0,
            int_optimized != 0, default_unit, ring,
            (out_ann && in_range) ? out_ann + (uint64_t)series * ann_stride
@@ -1000,19 +1064,25 @@ k_decode_batch(const uint8_t* __restrict__ blobs,
     };
 
     while (__any(running)) {
-        d.r.refill_issue(running);
-        /* NOT unrolled: the fully-inlined parser is ~10k instructions —
-         * eight copies would blow the instruction cache */
         /* wave-uniform capacity flag: cnt <= k + j, so the per-point
          * check matters only on a tile that could cross `stride` */
         const bool check_cap = k + DEC_TILE > stride;
+        /* NOT unrolled, neither loop: the fully-inlined parser is ~10k
+         * instructions — it is instantiated exactly once */
 #pragma unroll 1
-        for (uint32_t j = 0; j < DEC_TILE; j++) step(j, check_cap);
-        /* commit BEFORE the flush: the commit's counted vmcnt wait then
-         * covers only this tile's loads plus the PREVIOUS tile's stores
-         * (issued a whole tile ago, long retired) — never the 16 stores
-         * the flush is about to issue */
-        d.r.refill_commit();
+        for (uint32_t h = 0; h < DEC_TILE; h += RF_SPAN) {
+            /* scoped to one top-up span: the registers are written by the
+             * loads here and first read by the commit below, nothing in
+             * between */
+            const RingPending pd = d.r.refill_issue(running);
+#pragma unroll 1
+            for (uint32_t j = h; j < h + RF_SPAN; j++) step(j, check_cap);
+            /* the last commit comes BEFORE the flush: its vmcnt wait then
+             * covers only this span's loads plus the PREVIOUS tile's
+             * stores (issued a tile ago, long retired) — never the 16
+             * stores the flush is about to issue */
+            d.r.refill_commit(pd);
+        }
         flush(k);
         k += DEC_TILE;
     }
@@ -1818,7 +1888,7 @@ k_rollup_lane(const uint8_t* __restrict__ blobs,
     uint64_t* rring = rring_all[wave][lane];
 
     const bool in_range = series < nseries;
-    Decoder d;
+    RingDecoder d;
     d.init(blobs, in_range ? offsets[series] : 0, in_range ? lens[series] : 0,
            int_optimized != 0, default_unit, rring);
 
@@ -1928,9 +1998,9 @@ k_rollup_lane(const uint8_t* __restrict__ blobs,
     };
 
     while (__any(running)) {
-        d.r.refill_issue(running);
+        const RingPending pd = d.r.refill_issue(running);
 #pragma unroll 1
-        for (uint32_t jt = 0; jt < DEC_TILE; jt++) {
+        for (uint32_t jt = 0; jt < RF_SPAN; jt++) {
         if (running) {
             int64_t t;
             double v;
@@ -2032,7 +2102,7 @@ k_rollup_lane(const uint8_t* __restrict__ blobs,
             }
         }
         }
-        d.r.refill_commit();
+        d.r.refill_commit(pd);
     }
     if (in_range) out_errs[series] = err;
 }
