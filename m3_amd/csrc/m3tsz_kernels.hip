@@ -35,6 +35,7 @@
 #include <string.h>
 #include <stdio.h>
 #include "../../include/m3gpu.h"
+#include "rollup_plan.h" /* QCAP, MAX_AGGS, m3::RollupPlan + its host builder */
 
 /* ========================= shared constants ========================= */
 /* m3tsz.go:28-62, scheme.go:28-52, x/time/unit.go:30-42 */
@@ -1568,34 +1569,6 @@ k_encode_batch(const int64_t* __restrict__ ts, const double* __restrict__ vals,
  *                     M3GPU_SERIES_BUCKET_OVERFLOW.
  */
 
-#define QCAP 512 /* wave-kernel LDS staging capacity per series */
-#define MAX_AGGS 16
-
-struct RollupPlan {
-    int32_t agg_types[MAX_AGGS];
-    int8_t qidx[MAX_AGGS];   /* index into qs, or -1 */
-    double qs[MAX_AGGS];     /* sorted unique quantiles */
-    int32_t nq;
-    int32_t naggs;
-    /* Largest bucket size for which the production-default CKMS
-     * (eps=1e-3, insertAndCompressEvery=1024) provably never compresses
-     * for THIS quantile set, so its quantiles are exact order statistics
-     * (the calcQuantiles walk). Computed on the host; buckets beyond it
-     * flag M3GPU_SERIES_BUCKET_OVERFLOW rather than approximate. */
-    int32_t exact_cap;
-    /* Largest bucket size for which EVERY requested quantile resolves to
-     * the bucket MAX under the reference's walk (all-high quantile sets,
-     * e.g. p90+): the lane kernel then needs no value staging at all —
-     * running min/max suffice. 0 = extreme mode not applicable. */
-    int32_t extreme_cap;
-    /* CKMS stream options (quantile/cm/options.go:30-32 defaults:
-     * eps=1e-3, insertAndCompressEvery=1024); configurable via the
-     * *_opts ABI entries. every is capped at 1024 by validation (the
-     * deep-tier LDS buffers are sized for a 2*1024 peak). */
-    double eps;
-    int32_t every;
-};
-
 struct BucketState {
     int64_t isum, imin, imax, isumsq;
     double fsum, fsumsq, fmin, fmax, last;
@@ -2627,8 +2600,7 @@ k_rollup_ckms(const uint8_t* __restrict__ blobs,
 
 /* ============================ C-ABI host layer ============================ */
 
-#include <mutex>
-#include <climits>
+#include <memory>
 
 static __thread char g_err[512];
 static int g_device = 0;
@@ -2639,6 +2611,50 @@ static int set_hip_err(const char* what, hipError_t e) {
     return M3GPU_ERR_HIP;
 }
 #define HIP_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return set_hip_err(#expr, _e); } while (0)
+
+/* Owning device allocation of n elements: freed on every return path. */
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { (void)hipFree(p); }
+    hipError_t alloc(size_t n) {
+        (void)hipFree(p);
+        p = nullptr;
+        return hipMalloc(&p, n * sizeof(T));
+    }
+    /* alloc + blocking H2D copy */
+    hipError_t upload(const T* src, size_t n) {
+        hipError_t e = alloc(n);
+        return e != hipSuccess ? e
+             : hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice);
+    }
+    /* blocking D2H copy */
+    hipError_t download(T* dst, size_t n) const {
+        return hipMemcpy(dst, p, n * sizeof(T), hipMemcpyDeviceToHost);
+    }
+};
+
+/* the packed-stream inputs every decoding host form uploads */
+struct DevStreams {
+    DevBuf<uint8_t> blobs;
+    DevBuf<uint64_t> offsets;
+    DevBuf<uint32_t> lens;
+    hipError_t upload(const uint8_t* h_blobs, uint64_t blobs_len,
+                      const uint64_t* h_offsets, const uint32_t* h_lens,
+                      uint32_t nseries) {
+        hipError_t e = blobs.upload(h_blobs, blobs_len);
+        if (e == hipSuccess) e = offsets.upload(h_offsets, (size_t)nseries + 1);
+        if (e == hipSuccess) e = lens.upload(h_lens, nseries);
+        return e;
+    }
+};
+
+/* host scratch that cannot throw across the C boundary */
+struct FreeDeleter { void operator()(void* p) const { free(p); } };
 
 extern "C" {
 
@@ -2760,67 +2776,33 @@ int m3gpu_regather_dev(
     return M3GPU_OK;
 }
 
-static double agg_quantile_of_host(int32_t t) {
-    switch (t) {
-    case M3GPU_AGG_MEDIAN: case M3GPU_AGG_P50: return 0.5;
-    case M3GPU_AGG_P10: return 0.1;
-    case M3GPU_AGG_P20: return 0.2;
-    case M3GPU_AGG_P25: return 0.25;
-    case M3GPU_AGG_P30: return 0.3;
-    case M3GPU_AGG_P40: return 0.4;
-    case M3GPU_AGG_P60: return 0.6;
-    case M3GPU_AGG_P70: return 0.7;
-    case M3GPU_AGG_P75: return 0.75;
-    case M3GPU_AGG_P80: return 0.8;
-    case M3GPU_AGG_P90: return 0.9;
-    case M3GPU_AGG_P95: return 0.95;
-    case M3GPU_AGG_P99: return 0.99;
-    case M3GPU_AGG_P999: return 0.999;
-    case M3GPU_AGG_P9999: return 0.9999;
-    default: return -1.0;
-    }
+/* The plan builder's no-compression cap on its own (rollup_plan.h), for
+ * tests and host-side sizing. Aggs past MAX_AGGS are ignored. */
+int m3gpu_ckms_exact_cap(const int32_t* agg_types, int naggs, double eps) {
+    m3::RollupPlan plan;
+    m3::rollup_plan_build(agg_types, naggs < MAX_AGGS ? naggs : MAX_AGGS, eps,
+                          1024, &plan);
+    return plan.exact_cap;
 }
 
-/* Exported standalone form of the plan builder's no-compression cap (the
- * exact simulation of stream.go:362-385 thresholds; see the inline copy
- * in m3gpu_rollup_batch_dev_opts). For tests and host-side sizing. */
-extern "C" int m3gpu_ckms_exact_cap(const int32_t* agg_types, int naggs,
-                                    double eps) {
-    double qs[MAX_AGGS];
-    int nq = 0;
-    for (int i = 0; i < naggs && i < MAX_AGGS; i++) {
-        double q = agg_quantile_of_host(agg_types[i]);
-        if (q >= 0) qs[nq++] = q;
-    }
-    for (int i = 1; i < nq; i++) {
-        double k = qs[i];
-        int j = i - 1;
-        while (j >= 0 && qs[j] > k) { qs[j + 1] = qs[j]; j--; }
-        qs[j + 1] = k;
-    }
-    int m = 0;
-    for (int i = 0; i < nq; i++)
-        if (m == 0 || qs[m - 1] != qs[i]) qs[m++] = qs[i];
-    nq = m;
-    int cap = QCAP;
-    double eps2 = 2.0 * eps;
-    for (int v = 4; v <= QCAP + 1; v++) {
-        bool merges = false;
-        for (int mr = 0; mr <= v && !merges; mr++) {
-            long long thr = LLONG_MAX;
-            for (int i = 0; i < nq; i++) {
-                long long qmin;
-                if (mr >= (long long)(qs[i] * (double)v))
-                    qmin = (long long)(eps2 * (double)mr / qs[i]);
-                else
-                    qmin = (long long)(eps2 * (double)(v - mr) / (1.0 - qs[i]));
-                if (qmin < thr) thr = qmin;
-            }
-            if (nq > 0 && thr >= 2) merges = true;
-        }
-        if (merges) { cap = v - 1; break; }
-    }
-    return cap;
+/* Collect the series that d_errs flags M3GPU_SERIES_BUCKET_OVERFLOW into a
+ * device selection of *nsel indices (blocking copies; sel stays empty when
+ * there are none). */
+static int collect_overflow(const int32_t* d_errs, uint32_t nseries,
+                            DevBuf<int32_t>* sel, uint32_t* nsel) {
+    *nsel = 0;
+    std::unique_ptr<int32_t[], FreeDeleter> h(
+        (int32_t*)malloc(nseries * sizeof(int32_t)));
+    if (!h) { snprintf(g_err, sizeof(g_err), "oom"); return M3GPU_ERR_HIP; }
+    HIP_TRY(hipMemcpy(h.get(), d_errs, nseries * sizeof(int32_t),
+                      hipMemcpyDeviceToHost));
+    /* compact the flagged indices in place: k never passes i */
+    uint32_t k = 0;
+    for (uint32_t i = 0; i < nseries; i++)
+        if (h[i] == M3GPU_SERIES_BUCKET_OVERFLOW) h[k++] = (int32_t)i;
+    if (k) HIP_TRY(sel->upload(h.get(), k));
+    *nsel = k;
+    return M3GPU_OK;
 }
 
 int m3gpu_rollup_batch_dev_opts(
@@ -2841,132 +2823,7 @@ int m3gpu_rollup_batch_dev_opts(
         return M3GPU_ERR_BADARG;
     }
     m3::RollupPlan plan;
-    memset(&plan, 0, sizeof(plan));
-    plan.naggs = naggs;
-    plan.eps = eps;
-    plan.every = every;
-    /* sorted unique quantile list + per-agg mapping (timer stream is
-     * registered with the sorted unique quantile set) */
-    double qs[MAX_AGGS];
-    int nq = 0;
-    for (int i = 0; i < naggs; i++) {
-        plan.agg_types[i] = agg_types[i];
-        plan.qidx[i] = -1;
-        double q = -1;
-        switch (agg_types[i]) {
-        case M3GPU_AGG_MEDIAN: q = 0.5; break;
-        case M3GPU_AGG_P10: q = 0.1; break;
-        case M3GPU_AGG_P20: q = 0.2; break;
-        case M3GPU_AGG_P25: q = 0.25; break;
-        case M3GPU_AGG_P30: q = 0.3; break;
-        case M3GPU_AGG_P40: q = 0.4; break;
-        case M3GPU_AGG_P50: q = 0.5; break;
-        case M3GPU_AGG_P60: q = 0.6; break;
-        case M3GPU_AGG_P70: q = 0.7; break;
-        case M3GPU_AGG_P75: q = 0.75; break;
-        case M3GPU_AGG_P80: q = 0.8; break;
-        case M3GPU_AGG_P90: q = 0.9; break;
-        case M3GPU_AGG_P95: q = 0.95; break;
-        case M3GPU_AGG_P99: q = 0.99; break;
-        case M3GPU_AGG_P999: q = 0.999; break;
-        case M3GPU_AGG_P9999: q = 0.9999; break;
-        default: break;
-        }
-        if (q >= 0) { qs[nq++] = q; }
-    }
-    /* sort + dedupe */
-    for (int i = 1; i < nq; i++) {
-        double k = qs[i];
-        int j = i - 1;
-        while (j >= 0 && qs[j] > k) { qs[j + 1] = qs[j]; j--; }
-        qs[j + 1] = k;
-    }
-    int m = 0;
-    for (int i = 0; i < nq; i++)
-        if (m == 0 || qs[m - 1] != qs[i]) qs[m++] = qs[i];
-    nq = m;
-    plan.nq = nq;
-    for (int i = 0; i < nq; i++) plan.qs[i] = qs[i];
-    /* exact_cap: largest n such that for every numVals v <= n and every
-     * maxRank mr <= v, the compress merge threshold (stream.go:362-385,
-     * int64 truncation exactly as the reference computes it) stays < 2 =
-     * the minimum testVal — i.e. compression NEVER merges and quantiles
-     * are exact order statistics. */
-    plan.exact_cap = QCAP;
-    {
-        double eps2 = 2.0 * plan.eps;
-        for (int v = 4; v <= QCAP + 1; v++) /* minSamplesToCompress=3 */ {
-            bool merges = false;
-            for (int mr = 0; mr <= v && !merges; mr++) {
-                long long thr = LLONG_MAX;
-                for (int i = 0; i < nq; i++) {
-                    long long qmin;
-                    if (mr >= (long long)(qs[i] * (double)v))
-                        qmin = (long long)(eps2 * (double)mr / qs[i]);
-                    else
-                        qmin = (long long)(eps2 * (double)(v - mr) / (1.0 - qs[i]));
-                    if (qmin < thr) thr = qmin;
-                }
-                if (nq > 0 && thr >= 2) merges = true;
-            }
-            if (merges) { plan.exact_cap = v - 1; break; }
-        }
-    }
-    for (int i = 0; i < naggs; i++) {
-        double q = -1;
-        switch (agg_types[i]) {
-        case M3GPU_AGG_MEDIAN: case M3GPU_AGG_P50: q = 0.5; break;
-        case M3GPU_AGG_P10: q = 0.1; break;
-        case M3GPU_AGG_P20: q = 0.2; break;
-        case M3GPU_AGG_P25: q = 0.25; break;
-        case M3GPU_AGG_P30: q = 0.3; break;
-        case M3GPU_AGG_P40: q = 0.4; break;
-        case M3GPU_AGG_P60: q = 0.6; break;
-        case M3GPU_AGG_P70: q = 0.7; break;
-        case M3GPU_AGG_P75: q = 0.75; break;
-        case M3GPU_AGG_P80: q = 0.8; break;
-        case M3GPU_AGG_P90: q = 0.9; break;
-        case M3GPU_AGG_P95: q = 0.95; break;
-        case M3GPU_AGG_P99: q = 0.99; break;
-        case M3GPU_AGG_P999: q = 0.999; break;
-        case M3GPU_AGG_P9999: q = 0.9999; break;
-        default: break;
-        }
-        if (q >= 0)
-            for (int k = 0; k < nq; k++)
-                if (plan.qs[k] == q) { plan.qidx[i] = (int8_t)k; break; }
-    }
-
-    /* extreme_cap: largest n (bounded by exact_cap) for which EVERY
-     * requested quantile resolves to sorted[n-1] — the bucket max — in
-     * BOTH regimes the lane kernel reproduces (quantilesFromBuf for n<=3,
-     * the calcQuantiles walk with the k_{i-1}+1 shift above). All-high
-     * quantile sets (p90+, e.g. the sum/min/max/p99 rollup) then need no
-     * per-point value staging at all: running min/max suffice. */
-    plan.extreme_cap = 0;
-    if (nq > 0) {
-        int capn = plan.exact_cap < QCAP ? plan.exact_cap : QCAP;
-        for (int n = 1; n <= capn; n++) {
-            bool allmax = true;
-            if (n <= 3) {
-                for (int i = 0; i < nq && allmax; i++) {
-                    int idx = (int)(qs[i] * (double)n);
-                    if (idx >= n) idx = n - 1;
-                    if (idx != n - 1) allmax = false;
-                }
-            } else {
-                int kk = 0;
-                for (int i = 0; i < nq; i++) {
-                    int rank = (int)ceil(qs[i] * (double)n);
-                    kk = (i == 0) ? rank : ((rank > kk + 1) ? rank : kk + 1);
-                    int kc = kk > n ? n : kk;
-                    if (kc != n) { allmax = false; break; }
-                }
-            }
-            if (!allmax) break;
-            plan.extreme_cap = n;
-        }
-    }
+    m3::rollup_plan_build(agg_types, naggs, eps, every, &plan);
 
     hipStream_t s = (hipStream_t)hip_stream;
     bool with_q = plan.nq > 0 && metric_type == M3GPU_METRIC_TIMER;
@@ -2975,148 +2832,95 @@ int m3gpu_rollup_batch_dev_opts(
      * production-default eps has exact_cap 13, which bounds it) */
     bool extreme = with_q && plan.extreme_cap >= 8;
     /* metric type is a template parameter: dead per-metric BucketState
-     * fields drop out of the register file */
+     * fields drop out of the register file. Unknown metric types take the
+     * last branch. */
+    decltype(&m3::k_rollup_lane<RQ_NONE, M3GPU_METRIC_TIMER>) lane;
     if (extreme)
-        hipLaunchKernelGGL((m3::k_rollup_lane<RQ_EXTREME, M3GPU_METRIC_TIMER>),
-                           dim3(grid_lane(nseries)),
-                           dim3(BLOCK_THREADS), 0, s,
-                           d_blobs, d_offsets, d_lens, nseries, int_optimized,
-                           default_unit, window_ns, nbuckets, plan,
-                           d_out, d_out_window_ts, d_out_errs);
+        lane = m3::k_rollup_lane<RQ_EXTREME, M3GPU_METRIC_TIMER>;
     else if (with_q)
-        hipLaunchKernelGGL((m3::k_rollup_lane<RQ_STAGED, M3GPU_METRIC_TIMER>),
-                           dim3(grid_lane(nseries)),
-                           dim3(BLOCK_THREADS), 0, s,
-                           d_blobs, d_offsets, d_lens, nseries, int_optimized,
-                           default_unit, window_ns, nbuckets, plan,
-                           d_out, d_out_window_ts, d_out_errs);
+        lane = m3::k_rollup_lane<RQ_STAGED, M3GPU_METRIC_TIMER>;
     else if (metric_type == M3GPU_METRIC_COUNTER)
-        hipLaunchKernelGGL((m3::k_rollup_lane<RQ_NONE, M3GPU_METRIC_COUNTER>),
-                           dim3(grid_lane(nseries)),
-                           dim3(BLOCK_THREADS), 0, s,
-                           d_blobs, d_offsets, d_lens, nseries, int_optimized,
-                           default_unit, window_ns, nbuckets, plan,
-                           d_out, d_out_window_ts, d_out_errs);
+        lane = m3::k_rollup_lane<RQ_NONE, M3GPU_METRIC_COUNTER>;
     else if (metric_type == M3GPU_METRIC_GAUGE)
-        hipLaunchKernelGGL((m3::k_rollup_lane<RQ_NONE, M3GPU_METRIC_GAUGE>),
-                           dim3(grid_lane(nseries)),
-                           dim3(BLOCK_THREADS), 0, s,
-                           d_blobs, d_offsets, d_lens, nseries, int_optimized,
-                           default_unit, window_ns, nbuckets, plan,
-                           d_out, d_out_window_ts, d_out_errs);
+        lane = m3::k_rollup_lane<RQ_NONE, M3GPU_METRIC_GAUGE>;
     else
-        hipLaunchKernelGGL((m3::k_rollup_lane<RQ_NONE, M3GPU_METRIC_TIMER>),
-                           dim3(grid_lane(nseries)),
-                           dim3(BLOCK_THREADS), 0, s,
-                           d_blobs, d_offsets, d_lens, nseries, int_optimized,
-                           default_unit, window_ns, nbuckets, plan,
-                           d_out, d_out_window_ts, d_out_errs);
+        lane = m3::k_rollup_lane<RQ_NONE, M3GPU_METRIC_TIMER>;
+    hipLaunchKernelGGL(lane, dim3(grid_lane(nseries)), dim3(BLOCK_THREADS),
+                       0, s,
+                       d_blobs, d_offsets, d_lens, nseries, int_optimized,
+                       default_unit, window_ns, nbuckets, plan,
+                       d_out, d_out_window_ts, d_out_errs);
     HIP_TRY(hipGetLastError());
-    if (with_q) {
-        /* buckets deeper than the lane tier's capacity overflow to the
-         * wave-per-series kernel. The common case is zero overflows: test
-         * with a device-side count + 4-byte D2H instead of pulling and
-         * scanning the whole error array every call. */
-        /* process-lifetime scratch; atomics guard the one-time alloc
-         * (host entry points may be called from multiple threads) */
-        static std::atomic<uint32_t*> g_ovf{nullptr};
-        uint32_t* d_ovf = g_ovf.load(std::memory_order_acquire);
-        if (!d_ovf) {
-            uint32_t* fresh = nullptr;
-            HIP_TRY(hipMalloc(&fresh, sizeof(uint32_t)));
-            uint32_t* expected = nullptr;
-            if (!g_ovf.compare_exchange_strong(expected, fresh,
-                                               std::memory_order_acq_rel)) {
-                (void)hipFree(fresh); /* another thread won the race */
-            }
-            d_ovf = g_ovf.load(std::memory_order_acquire);
-        }
-        HIP_TRY(hipMemsetAsync(d_ovf, 0, sizeof(uint32_t), s));
-        hipLaunchKernelGGL(m3::k_count_errcode, dim3(256), dim3(BLOCK_THREADS),
-                           0, s, d_out_errs, nseries,
-                           M3GPU_SERIES_BUCKET_OVERFLOW, d_ovf);
-        HIP_TRY(hipGetLastError());
-        uint32_t h_ovf = 0;
-        HIP_TRY(hipMemcpyAsync(&h_ovf, d_ovf, sizeof(uint32_t),
-                               hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (h_ovf == 0) return M3GPU_OK;
-        int32_t* h_errs = (int32_t*)malloc(nseries * sizeof(int32_t));
-        if (!h_errs) { snprintf(g_err, sizeof(g_err), "oom"); return M3GPU_ERR_HIP; }
-        hipError_t ce = hipMemcpy(h_errs, d_out_errs, nseries * sizeof(int32_t),
-                                  hipMemcpyDeviceToHost);
-        if (ce != hipSuccess) { free(h_errs); return set_hip_err("errs copy", ce); }
-        uint32_t nretry = 0;
-        for (uint32_t i = 0; i < nseries; i++)
-            if (h_errs[i] == M3GPU_SERIES_BUCKET_OVERFLOW) nretry++;
-        if (nretry) {
-            int32_t* h_sel = (int32_t*)malloc(nretry * sizeof(int32_t));
-            uint32_t k = 0;
-            for (uint32_t i = 0; i < nseries; i++)
-                if (h_errs[i] == M3GPU_SERIES_BUCKET_OVERFLOW) h_sel[k++] = (int32_t)i;
-            int32_t* d_sel = nullptr;
-            hipError_t e2 = hipMalloc(&d_sel, nretry * sizeof(int32_t));
-            if (e2 == hipSuccess)
-                e2 = hipMemcpy(d_sel, h_sel, nretry * sizeof(int32_t), hipMemcpyHostToDevice);
-            if (e2 == hipSuccess) {
-                hipLaunchKernelGGL(m3::k_rollup_batch, dim3(grid_for(nretry)),
-                                   dim3(BLOCK_THREADS), 0, s,
-                                   d_blobs, d_offsets, d_lens, d_sel, nretry,
-                                   int_optimized, default_unit, metric_type,
-                                   window_ns, nbuckets, plan,
-                                   d_out, d_out_window_ts, d_out_errs);
-                e2 = hipGetLastError();
-                if (e2 == hipSuccess) e2 = hipStreamSynchronize(s);
-            }
-            (void)hipFree(d_sel);
-            free(h_sel);
-            if (e2 != hipSuccess) { free(h_errs); return set_hip_err("rollup retry", e2); }
+    if (!with_q) return M3GPU_OK;
 
-            /* Third tier: buckets deeper than the exact-order-statistics cap
-             * run the real compressed CKMS (k_rollup_ckms, one series per
-             * workgroup, ~122 KB dynamic LDS). Rescan the error flags the
-             * wave kernel just rewrote. */
-            ce = hipMemcpy(h_errs, d_out_errs, nseries * sizeof(int32_t),
-                           hipMemcpyDeviceToHost);
-            if (ce != hipSuccess) { free(h_errs); return set_hip_err("errs copy2", ce); }
-            uint32_t ndeep = 0;
-            for (uint32_t i = 0; i < nseries; i++)
-                if (h_errs[i] == M3GPU_SERIES_BUCKET_OVERFLOW) ndeep++;
-            if (ndeep) {
-                size_t lds_bytes = (size_t)CKMS_CAP * 32 /* val+nr+dl x2 */
-                                 + (size_t)CKMS_BUF * 24 /* less+more+sorted */
-                                 + (size_t)MAX_AGGS * 24; /* computed+thr */
-                hipError_t e3 = hipFuncSetAttribute(
-                    reinterpret_cast<const void*>(m3::k_rollup_ckms),
-                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-                int32_t* h_sel2 = (int32_t*)malloc(ndeep * sizeof(int32_t));
-                uint32_t k2 = 0;
-                for (uint32_t i = 0; i < nseries; i++)
-                    if (h_errs[i] == M3GPU_SERIES_BUCKET_OVERFLOW)
-                        h_sel2[k2++] = (int32_t)i;
-                int32_t* d_sel2 = nullptr;
-                if (e3 == hipSuccess) e3 = hipMalloc(&d_sel2, ndeep * sizeof(int32_t));
-                if (e3 == hipSuccess)
-                    e3 = hipMemcpy(d_sel2, h_sel2, ndeep * sizeof(int32_t),
-                                   hipMemcpyHostToDevice);
-                if (e3 == hipSuccess) {
-                    hipLaunchKernelGGL(m3::k_rollup_ckms, dim3(ndeep),
-                                       dim3(CKMS_BLOCK), lds_bytes, s,
-                                       d_blobs, d_offsets, d_lens, d_sel2, ndeep,
-                                       int_optimized, default_unit,
-                                       window_ns, nbuckets, plan,
-                                       d_out, d_out_window_ts, d_out_errs);
-                    e3 = hipGetLastError();
-                    if (e3 == hipSuccess) e3 = hipStreamSynchronize(s);
-                }
-                (void)hipFree(d_sel2);
-                free(h_sel2);
-                if (e3 != hipSuccess) { free(h_errs); return set_hip_err("rollup ckms", e3); }
-            }
+    /* buckets deeper than the lane tier's capacity overflow to the
+     * wave-per-series kernel. The common case is zero overflows: test
+     * with a device-side count + 4-byte D2H instead of pulling and
+     * scanning the whole error array every call. */
+    /* process-lifetime scratch; atomics guard the one-time alloc
+     * (host entry points may be called from multiple threads). One word
+     * for every stream and device: splitting it is a separate change. */
+    static std::atomic<uint32_t*> g_ovf{nullptr};
+    uint32_t* d_ovf = g_ovf.load(std::memory_order_acquire);
+    if (!d_ovf) {
+        uint32_t* fresh = nullptr;
+        HIP_TRY(hipMalloc(&fresh, sizeof(uint32_t)));
+        uint32_t* expected = nullptr;
+        if (!g_ovf.compare_exchange_strong(expected, fresh,
+                                           std::memory_order_acq_rel)) {
+            (void)hipFree(fresh); /* another thread won the race */
         }
-        free(h_errs);
+        d_ovf = g_ovf.load(std::memory_order_acquire);
     }
-    return M3GPU_OK;
+    HIP_TRY(hipMemsetAsync(d_ovf, 0, sizeof(uint32_t), s));
+    hipLaunchKernelGGL(m3::k_count_errcode, dim3(256), dim3(BLOCK_THREADS),
+                       0, s, d_out_errs, nseries,
+                       M3GPU_SERIES_BUCKET_OVERFLOW, d_ovf);
+    HIP_TRY(hipGetLastError());
+    uint32_t h_ovf = 0;
+    HIP_TRY(hipMemcpyAsync(&h_ovf, d_ovf, sizeof(uint32_t),
+                           hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (h_ovf == 0) return M3GPU_OK;
+
+    /* One retry tier: rerun the series still flagged as overflowed on the
+     * wave-per-series kernel, or (ckms) on the real compressed CKMS
+     * (k_rollup_ckms, one series per workgroup, ~122 KB dynamic LDS), and
+     * wait for it, since the next step reads the flags it rewrites. */
+    auto run_tier = [&](bool ckms) -> int {
+        DevBuf<int32_t> sel;
+        uint32_t n = 0;
+        int rc = collect_overflow(d_out_errs, nseries, &sel, &n);
+        if (rc != M3GPU_OK || n == 0) return rc;
+        if (!ckms) {
+            hipLaunchKernelGGL(m3::k_rollup_batch, dim3(grid_for(n)),
+                               dim3(BLOCK_THREADS), 0, s,
+                               d_blobs, d_offsets, d_lens, sel.p, n,
+                               int_optimized, default_unit, metric_type,
+                               window_ns, nbuckets, plan,
+                               d_out, d_out_window_ts, d_out_errs);
+        } else {
+            size_t lds_bytes = (size_t)CKMS_CAP * 32 /* val+nr+dl x2 */
+                             + (size_t)CKMS_BUF * 24 /* less+more+sorted */
+                             + (size_t)MAX_AGGS * 24; /* computed+thr */
+            HIP_TRY(hipFuncSetAttribute(
+                reinterpret_cast<const void*>(m3::k_rollup_ckms),
+                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+            hipLaunchKernelGGL(m3::k_rollup_ckms, dim3(n),
+                               dim3(CKMS_BLOCK), lds_bytes, s,
+                               d_blobs, d_offsets, d_lens, sel.p, n,
+                               int_optimized, default_unit,
+                               window_ns, nbuckets, plan,
+                               d_out, d_out_window_ts, d_out_errs);
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(s));
+        return M3GPU_OK;
+    };
+    int rc = run_tier(false);
+    /* buckets deeper than the exact-order-statistics cap */
+    if (rc == M3GPU_OK) rc = run_tier(true);
+    return rc;
 }
 
 int m3gpu_rollup_batch_dev(
@@ -3154,45 +2958,63 @@ int m3gpu_merge_batch_dev(
 
 /* ---------- host-pointer convenience forms (the cgo surface) ---------- */
 
+/* Both decode forms: upload the streams, decode on the null stream, copy
+ * the results back. with_ann selects the annotation-capturing entry. */
+static int decode_host(
+    const uint8_t* blobs, uint64_t blobs_len,
+    const uint64_t* offsets, const uint32_t* lens,
+    uint32_t nseries, int int_optimized, uint8_t default_unit,
+    int64_t* out_ts, double* out_vals, uint32_t* out_counts,
+    int32_t* out_errs, uint32_t stride,
+    bool with_ann, uint8_t* out_ann, uint32_t ann_stride) {
+    DevStreams in;
+    DevBuf<int64_t> d_ts;
+    DevBuf<double> d_vals;
+    DevBuf<uint32_t> d_counts;
+    DevBuf<int32_t> d_errs;
+    DevBuf<uint8_t> d_ann;
+    uint64_t npts = (uint64_t)nseries * stride;
+    uint64_t ann_total = (uint64_t)nseries * ann_stride;
+    HIP_TRY(in.upload(blobs, blobs_len, offsets, lens, nseries));
+    HIP_TRY(d_ts.alloc(npts));
+    HIP_TRY(d_vals.alloc(npts));
+    HIP_TRY(d_counts.alloc(nseries));
+    HIP_TRY(d_errs.alloc(nseries));
+    int rc;
+    if (with_ann) {
+        HIP_TRY(d_ann.alloc(ann_total));
+        HIP_TRY(hipMemset(d_ann.p, 0, ann_total));
+        rc = m3gpu_decode_batch_dev_ann(
+            in.blobs.p, in.offsets.p, in.lens.p, nseries, int_optimized,
+            default_unit, d_ts.p, d_vals.p, d_counts.p, d_errs.p, stride,
+            d_ann.p, ann_stride, nullptr);
+    } else {
+        rc = m3gpu_decode_batch_dev(
+            in.blobs.p, in.offsets.p, in.lens.p, nseries, int_optimized,
+            default_unit, d_ts.p, d_vals.p, d_counts.p, d_errs.p, stride,
+            nullptr);
+    }
+    if (rc != M3GPU_OK) return rc;
+    HIP_TRY(d_ts.download(out_ts, npts));
+    HIP_TRY(d_vals.download(out_vals, npts));
+    HIP_TRY(d_counts.download(out_counts, nseries));
+    HIP_TRY(d_errs.download(out_errs, nseries));
+    if (with_ann) HIP_TRY(d_ann.download(out_ann, ann_total));
+    return M3GPU_OK;
+}
+
 int m3gpu_decode_batch(
     const uint8_t* blobs, uint64_t blobs_len,
     const uint64_t* offsets, const uint32_t* lens,
     uint32_t nseries, int int_optimized, uint8_t default_unit,
     int64_t* out_ts, double* out_vals, uint32_t* out_counts,
     int32_t* out_errs, uint32_t stride) {
-    uint8_t* d_blobs = nullptr;
-    uint64_t* d_offsets = nullptr;
-    uint32_t* d_lens = nullptr;
-    int64_t* d_ts = nullptr;
-    double* d_vals = nullptr;
-    uint32_t* d_counts = nullptr;
-    int32_t* d_errs = nullptr;
-    uint64_t npts = (uint64_t)nseries * stride;
-    int rc = M3GPU_OK;
-    HIP_TRY(hipMalloc(&d_blobs, blobs_len));
-    HIP_TRY(hipMalloc(&d_offsets, (nseries + 1) * sizeof(uint64_t)));
-    HIP_TRY(hipMalloc(&d_lens, nseries * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&d_ts, npts * sizeof(int64_t)));
-    HIP_TRY(hipMalloc(&d_vals, npts * sizeof(double)));
-    HIP_TRY(hipMalloc(&d_counts, nseries * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&d_errs, nseries * sizeof(int32_t)));
-    HIP_TRY(hipMemcpy(d_blobs, blobs, blobs_len, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_offsets, offsets, (nseries + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_lens, lens, nseries * sizeof(uint32_t), hipMemcpyHostToDevice));
-    rc = m3gpu_decode_batch_dev(d_blobs, d_offsets, d_lens, nseries,
-                                int_optimized, default_unit, d_ts, d_vals,
-                                d_counts, d_errs, stride, nullptr);
-    if (rc == M3GPU_OK) {
-        HIP_TRY(hipMemcpy(out_ts, d_ts, npts * sizeof(int64_t), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(out_vals, d_vals, npts * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(out_counts, d_counts, nseries * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(out_errs, d_errs, nseries * sizeof(int32_t), hipMemcpyDeviceToHost));
-    }
-    (void)hipFree(d_blobs); (void)hipFree(d_offsets); (void)hipFree(d_lens);
-    (void)hipFree(d_ts); (void)hipFree(d_vals); (void)hipFree(d_counts); (void)hipFree(d_errs);
-    return rc;
+    return decode_host(blobs, blobs_len, offsets, lens, nseries,
+                       int_optimized, default_unit, out_ts, out_vals,
+                       out_counts, out_errs, stride, false, nullptr, 0);
 }
 
+/* what a cgo ReaderIterator shim calls for annotation-bearing blocks */
 int m3gpu_decode_batch_ann(
     const uint8_t* blobs, uint64_t blobs_len,
     const uint64_t* offsets, const uint32_t* lens,
@@ -3200,46 +3022,10 @@ int m3gpu_decode_batch_ann(
     int64_t* out_ts, double* out_vals, uint32_t* out_counts,
     int32_t* out_errs, uint32_t stride,
     uint8_t* out_ann, uint32_t ann_stride) {
-    /* host-pointer convenience form of m3gpu_decode_batch_dev_ann (what a
-     * cgo ReaderIterator shim calls for annotation-bearing blocks) */
-    uint8_t* d_blobs = nullptr;
-    uint64_t* d_offsets = nullptr;
-    uint32_t* d_lens = nullptr;
-    int64_t* d_ts = nullptr;
-    double* d_vals = nullptr;
-    uint32_t* d_counts = nullptr;
-    int32_t* d_errs = nullptr;
-    uint8_t* d_ann = nullptr;
-    uint64_t npts = (uint64_t)nseries * stride;
-    uint64_t ann_total = (uint64_t)nseries * ann_stride;
-    int rc = M3GPU_OK;
-    HIP_TRY(hipMalloc(&d_blobs, blobs_len));
-    HIP_TRY(hipMalloc(&d_offsets, (nseries + 1) * sizeof(uint64_t)));
-    HIP_TRY(hipMalloc(&d_lens, nseries * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&d_ts, npts * sizeof(int64_t)));
-    HIP_TRY(hipMalloc(&d_vals, npts * sizeof(double)));
-    HIP_TRY(hipMalloc(&d_counts, nseries * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&d_errs, nseries * sizeof(int32_t)));
-    HIP_TRY(hipMalloc(&d_ann, ann_total));
-    HIP_TRY(hipMemset(d_ann, 0, ann_total));
-    HIP_TRY(hipMemcpy(d_blobs, blobs, blobs_len, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_offsets, offsets, (nseries + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_lens, lens, nseries * sizeof(uint32_t), hipMemcpyHostToDevice));
-    rc = m3gpu_decode_batch_dev_ann(d_blobs, d_offsets, d_lens, nseries,
-                                    int_optimized, default_unit, d_ts, d_vals,
-                                    d_counts, d_errs, stride, d_ann,
-                                    ann_stride, nullptr);
-    if (rc == M3GPU_OK) {
-        HIP_TRY(hipMemcpy(out_ts, d_ts, npts * sizeof(int64_t), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(out_vals, d_vals, npts * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(out_counts, d_counts, nseries * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(out_errs, d_errs, nseries * sizeof(int32_t), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(out_ann, d_ann, ann_total, hipMemcpyDeviceToHost));
-    }
-    (void)hipFree(d_blobs); (void)hipFree(d_offsets); (void)hipFree(d_lens);
-    (void)hipFree(d_ts); (void)hipFree(d_vals); (void)hipFree(d_counts);
-    (void)hipFree(d_errs); (void)hipFree(d_ann);
-    return rc;
+    return decode_host(blobs, blobs_len, offsets, lens, nseries,
+                       int_optimized, default_unit, out_ts, out_vals,
+                       out_counts, out_errs, stride, true, out_ann,
+                       ann_stride);
 }
 
 int m3gpu_encode_batch(
@@ -3247,36 +3033,28 @@ int m3gpu_encode_batch(
     uint32_t nseries, uint32_t stride, int int_optimized, uint8_t unit,
     uint8_t* out_bytes, uint32_t out_stride, uint32_t* out_lens,
     int32_t* out_errs) {
-    int64_t* d_ts = nullptr;
-    double* d_vals = nullptr;
-    uint32_t* d_counts = nullptr;
-    uint8_t* d_out = nullptr;
-    uint32_t* d_lens = nullptr;
-    int32_t* d_errs = nullptr;
+    DevBuf<int64_t> d_ts;
+    DevBuf<double> d_vals;
+    DevBuf<uint32_t> d_counts, d_lens;
+    DevBuf<uint8_t> d_out;
+    DevBuf<int32_t> d_errs;
     uint64_t npts = (uint64_t)nseries * stride;
     uint64_t outb = (uint64_t)nseries * out_stride;
-    int rc;
-    HIP_TRY(hipMalloc(&d_ts, npts * sizeof(int64_t)));
-    HIP_TRY(hipMalloc(&d_vals, npts * sizeof(double)));
-    HIP_TRY(hipMalloc(&d_counts, nseries * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&d_out, outb));
-    HIP_TRY(hipMalloc(&d_lens, nseries * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&d_errs, nseries * sizeof(int32_t)));
-    HIP_TRY(hipMemcpy(d_ts, ts, npts * sizeof(int64_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_vals, vals, npts * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_counts, counts, nseries * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(d_out, 0, outb));
-    rc = m3gpu_encode_batch_dev(d_ts, d_vals, d_counts, nseries, stride,
-                                int_optimized, unit, d_out, out_stride,
-                                d_lens, d_errs, nullptr);
-    if (rc == M3GPU_OK) {
-        HIP_TRY(hipMemcpy(out_bytes, d_out, outb, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(out_lens, d_lens, nseries * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(out_errs, d_errs, nseries * sizeof(int32_t), hipMemcpyDeviceToHost));
-    }
-    (void)hipFree(d_ts); (void)hipFree(d_vals); (void)hipFree(d_counts);
-    (void)hipFree(d_out); (void)hipFree(d_lens); (void)hipFree(d_errs);
-    return rc;
+    HIP_TRY(d_ts.upload(ts, npts));
+    HIP_TRY(d_vals.upload(vals, npts));
+    HIP_TRY(d_counts.upload(counts, nseries));
+    HIP_TRY(d_out.alloc(outb));
+    HIP_TRY(hipMemset(d_out.p, 0, outb));
+    HIP_TRY(d_lens.alloc(nseries));
+    HIP_TRY(d_errs.alloc(nseries));
+    int rc = m3gpu_encode_batch_dev(d_ts.p, d_vals.p, d_counts.p, nseries,
+                                    stride, int_optimized, unit, d_out.p,
+                                    out_stride, d_lens.p, d_errs.p, nullptr);
+    if (rc != M3GPU_OK) return rc;
+    HIP_TRY(d_out.download(out_bytes, outb));
+    HIP_TRY(d_lens.download(out_lens, nseries));
+    HIP_TRY(d_errs.download(out_errs, nseries));
+    return M3GPU_OK;
 }
 
 int m3gpu_rollup_batch(
@@ -3286,36 +3064,26 @@ int m3gpu_rollup_batch(
     int metric_type, int64_t window_ns, uint32_t nbuckets,
     const int32_t* agg_types, int naggs,
     double* out, int64_t* out_window_ts, int32_t* out_errs) {
-    uint8_t* d_blobs = nullptr;
-    uint64_t* d_offsets = nullptr;
-    uint32_t* d_lens = nullptr;
-    double* d_out = nullptr;
-    int64_t* d_wts = nullptr;
-    int32_t* d_errs = nullptr;
-    uint64_t nout = (uint64_t)nseries * nbuckets * naggs;
-    int rc;
-    HIP_TRY(hipMalloc(&d_blobs, blobs_len));
-    HIP_TRY(hipMalloc(&d_offsets, (nseries + 1) * sizeof(uint64_t)));
-    HIP_TRY(hipMalloc(&d_lens, nseries * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&d_out, nout * sizeof(double)));
-    HIP_TRY(hipMalloc(&d_wts, (uint64_t)nseries * nbuckets * sizeof(int64_t)));
-    HIP_TRY(hipMalloc(&d_errs, nseries * sizeof(int32_t)));
-    HIP_TRY(hipMemcpy(d_blobs, blobs, blobs_len, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_offsets, offsets, (nseries + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_lens, lens, nseries * sizeof(uint32_t), hipMemcpyHostToDevice));
-    rc = m3gpu_rollup_batch_dev(d_blobs, d_offsets, d_lens, nseries,
-                                int_optimized, default_unit, metric_type,
-                                window_ns, nbuckets, agg_types, naggs,
-                                d_out, d_wts, d_errs, nullptr);
-    if (rc == M3GPU_OK) {
-        HIP_TRY(hipMemcpy(out, d_out, nout * sizeof(double), hipMemcpyDeviceToHost));
-        if (out_window_ts)
-            HIP_TRY(hipMemcpy(out_window_ts, d_wts, (uint64_t)nseries * nbuckets * sizeof(int64_t), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(out_errs, d_errs, nseries * sizeof(int32_t), hipMemcpyDeviceToHost));
-    }
-    (void)hipFree(d_blobs); (void)hipFree(d_offsets); (void)hipFree(d_lens);
-    (void)hipFree(d_out); (void)hipFree(d_wts); (void)hipFree(d_errs);
-    return rc;
+    DevStreams in;
+    DevBuf<double> d_out;
+    DevBuf<int64_t> d_wts;
+    DevBuf<int32_t> d_errs;
+    uint64_t nwin = (uint64_t)nseries * nbuckets;
+    uint64_t nout = nwin * naggs;
+    HIP_TRY(in.upload(blobs, blobs_len, offsets, lens, nseries));
+    HIP_TRY(d_out.alloc(nout));
+    HIP_TRY(d_wts.alloc(nwin));
+    HIP_TRY(d_errs.alloc(nseries));
+    int rc = m3gpu_rollup_batch_dev(in.blobs.p, in.offsets.p, in.lens.p,
+                                    nseries, int_optimized, default_unit,
+                                    metric_type, window_ns, nbuckets,
+                                    agg_types, naggs, d_out.p, d_wts.p,
+                                    d_errs.p, nullptr);
+    if (rc != M3GPU_OK) return rc;
+    HIP_TRY(d_out.download(out, nout));
+    if (out_window_ts) HIP_TRY(d_wts.download(out_window_ts, nwin));
+    HIP_TRY(d_errs.download(out_errs, nseries));
+    return M3GPU_OK;
 }
 
 } /* extern "C" */
