@@ -134,7 +134,8 @@ int m3gpu_decode_batch(
  * row); start time = first timestamp (as dbnode series buffers do). Output:
  * stream bytes at d_out_bytes + i*out_stride (finalized, EOS tail included),
  * length in out_lens[i]. out_stride must be a multiple of 8 and hold the
- * worst case (~20 B/pt + 16). Fixed unit, no annotations (bulk path). */
+ * worst case (~20 B/pt + 16). This is the bulk path: one unit for every
+ * point and no annotations. m3gpu_encode_batch_full_dev below takes both. */
 int m3gpu_encode_batch_dev(
     const int64_t* d_ts, const double* d_vals, const uint32_t* d_counts,
     uint32_t nseries, uint32_t stride, int int_optimized, uint8_t unit,
@@ -144,6 +145,56 @@ int m3gpu_encode_batch_dev(
 int m3gpu_encode_batch(
     const int64_t* ts, const double* vals, const uint32_t* counts,
     uint32_t nseries, uint32_t stride, int int_optimized, uint8_t unit,
+    uint8_t* out_bytes, uint32_t out_stride, uint32_t* out_lens,
+    int32_t* out_errs);
+
+/* Full encode: the batched form of Encoder.Encode(dp, tu, ant)
+ * (src/dbnode/encoding/m3tsz/encoder.go:90) with the timestamp semantics of
+ * timestamp_encoder.go:72-195. Points, counts and outputs are as in
+ * m3gpu_encode_batch_dev; three optional inputs are added, each of which may
+ * be NULL:
+ *  - d_units [nseries*stride]: the unit of every point. A valid unit that
+ *    differs from the current one writes the time-unit marker, the unit byte
+ *    and a 64-bit nanosecond delta-of-delta. A point whose unit is invalid,
+ *    or stays at a unit without a time scheme (5..8), fails its series with
+ *    M3GPU_SERIES_NO_SCHEME. NULL: every point uses default_unit.
+ *  - d_start_ns [nseries]: the block start. It is what the first 64 bits of
+ *    the stream hold, and initialTimeUnit(start, default_unit) is the unit
+ *    the stream starts in. NULL: the series' first timestamp.
+ *  - d_ann: one region of ann_stride bytes per series (4-byte aligned,
+ *    ann_stride a multiple of 4 and >= 16), in the layout
+ *    m3gpu_decode_batch_dev_ann writes:
+ *      [u32 n_events][n_events x {u32 point, u32 off, u32 len}][...bytes]
+ *    so a decoded region can be passed back unchanged. `point` must be
+ *    strictly increasing and < counts[i]; off + len must lie inside the
+ *    region; len == 0 means no annotation. An annotation is written before
+ *    its point iff it is non-empty and its XXH64 differs from that of the
+ *    last one written (so a repeated annotation is written once). A region
+ *    that breaks a rule fails its series with M3GPU_SERIES_ANNOTATION before
+ *    any annotation byte is read. NULL (with ann_stride 0): no annotations.
+ * With all three NULL the output equals m3gpu_encode_batch_dev's.
+ * Worst-case stream size of a series, which out_stride must hold: the bulk
+ * bound (~20 B/pt + 16), plus 11 bits + up to 5 varint bytes + len bytes per
+ * annotation written, plus 19 bits + 64 bits per unit change. A series that
+ * does not fit fails with M3GPU_SERIES_CAPACITY; other series are unaffected.
+ * M3GPU_ERR_BADARG, before any work is queued: out_stride not a multiple of
+ * 8; d_ann given with ann_stride % 4 != 0 or ann_stride < 16, or itself not
+ * 4-byte aligned; d_ann NULL with ann_stride != 0. */
+int m3gpu_encode_batch_full_dev(
+    const int64_t* d_ts, const double* d_vals, const uint32_t* d_counts,
+    const uint8_t* d_units,      /* [nseries*stride], NULL => default_unit  */
+    const int64_t* d_start_ns,   /* [nseries], NULL => first timestamp      */
+    const uint8_t* d_ann, uint32_t ann_stride, /* NULL,0 => no annotations  */
+    uint32_t nseries, uint32_t stride, int int_optimized, uint8_t default_unit,
+    uint8_t* d_out_bytes, uint32_t out_stride, uint32_t* d_out_lens,
+    int32_t* d_out_errs, void* hip_stream);
+
+/* host-pointer convenience form of the full encode */
+int m3gpu_encode_batch_full(
+    const int64_t* ts, const double* vals, const uint32_t* counts,
+    const uint8_t* units, const int64_t* start_ns,
+    const uint8_t* ann, uint32_t ann_stride,
+    uint32_t nseries, uint32_t stride, int int_optimized, uint8_t default_unit,
     uint8_t* out_bytes, uint32_t out_stride, uint32_t* out_lens,
     int32_t* out_errs);
 

@@ -226,3 +226,123 @@ func DecodeBatchAnn(
 	}
 	return ts, vals, counts, errs, anns, nil
 }
+
+// annRegionSize is the bytes one series' events need in an annotation
+// region: the event count, one 12-byte table entry per event, the bytes.
+func annRegionSize(evs []AnnotationEvent) uint64 {
+	n := uint64(4)
+	for _, ev := range evs {
+		n += 12 + uint64(len(ev.Bytes))
+	}
+	return n
+}
+
+// buildAnnRegions lays every series' events out in the region layout of
+// m3gpu.h (the one DecodeBatchAnn parses), annStride bytes per series. It
+// returns an error, and writes nothing out of bounds, when a series' events
+// do not fit annStride or their points are not strictly increasing and below
+// the series' count.
+func buildAnnRegions(
+	anns [][]AnnotationEvent, counts []uint32, annStride uint32,
+) ([]byte, error) {
+	if annStride%4 != 0 || annStride < 16 {
+		return nil, errors.New("m3gpu: annStride must be 4-aligned and >= 16")
+	}
+	region := make([]byte, uint64(len(anns))*uint64(annStride))
+	le := binary.LittleEndian
+	for i, evs := range anns {
+		if annRegionSize(evs) > uint64(annStride) {
+			return nil, errors.New("m3gpu: annotations do not fit annStride")
+		}
+		r := region[uint64(i)*uint64(annStride) : uint64(i+1)*uint64(annStride)]
+		le.PutUint32(r[0:4], uint32(len(evs)))
+		tail := annStride
+		for j, ev := range evs {
+			if ev.Point >= counts[i] || (j > 0 && ev.Point <= evs[j-1].Point) {
+				return nil, errors.New("m3gpu: annotation points must be " +
+					"strictly increasing and below the series' count")
+			}
+			tail -= uint32(len(ev.Bytes))
+			copy(r[tail:], ev.Bytes)
+			e := r[4+j*12 : 4+j*12+12]
+			le.PutUint32(e[0:4], ev.Point)
+			le.PutUint32(e[4:8], tail)
+			le.PutUint32(e[8:12], uint32(len(ev.Bytes)))
+		}
+	}
+	return region, nil
+}
+
+// EncodeBatchFull is the batched form of Encoder.Encode(dp, tu, ant)
+// (dbnode/encoding/m3tsz/encoder.go:90; timestamp_encoder.go:72-195): like
+// EncodeBatch, with each point's own time unit, per-series annotation
+// events (what DecodeBatchAnn returns can be passed back unchanged) and an
+// explicit block start per series. units (len n*stride), startNs (len n)
+// and anns (len n) may each be nil: default unit for every point, start =
+// first timestamp, no annotations. outStride must hold the worst case given
+// in m3gpu.h (EncodeBatch's bound, plus 7 bytes + len per annotation, plus
+// 11 bytes per unit change).
+func EncodeBatchFull(
+	ts []int64, vals []float64, counts []uint32,
+	units []byte, startNs []int64, anns [][]AnnotationEvent,
+	stride uint32, intOptimized bool, defaultUnit byte, outStride uint32,
+) (streams []byte, lens []uint32, errs []SeriesError, err error) {
+	n := uint32(len(counts))
+	if n == 0 {
+		return nil, nil, nil, nil
+	}
+	npts := uint64(n) * uint64(stride)
+	if uint64(len(ts)) < npts || uint64(len(vals)) < npts ||
+		(units != nil && uint64(len(units)) < npts) ||
+		(startNs != nil && uint32(len(startNs)) < n) ||
+		(anns != nil && uint32(len(anns)) != n) {
+		return nil, nil, nil, errors.New("m3gpu: input slices shorter than the batch")
+	}
+	var unitsPtr *C.uint8_t
+	if units != nil {
+		unitsPtr = (*C.uint8_t)(unsafe.Pointer(&units[0]))
+	}
+	var startPtr *C.int64_t
+	if startNs != nil {
+		startPtr = (*C.int64_t)(unsafe.Pointer(&startNs[0]))
+	}
+	var annPtr *C.uint8_t
+	annStride := uint32(0)
+	if anns != nil {
+		need := uint64(16)
+		for _, evs := range anns {
+			if s := annRegionSize(evs); s > need {
+				need = s
+			}
+		}
+		if need > 1<<31 {
+			return nil, nil, nil, errors.New("m3gpu: annotations too large")
+		}
+		annStride = (uint32(need) + 3) &^ 3
+		region, rerr := buildAnnRegions(anns, counts, annStride)
+		if rerr != nil {
+			return nil, nil, nil, rerr
+		}
+		annPtr = (*C.uint8_t)(unsafe.Pointer(&region[0]))
+	}
+	streams = make([]byte, uint64(n)*uint64(outStride))
+	lens = make([]uint32, n)
+	errs = make([]SeriesError, n)
+	intOpt := C.int(0)
+	if intOptimized {
+		intOpt = 1
+	}
+	rc := C.m3gpu_encode_batch_full(
+		(*C.int64_t)(unsafe.Pointer(&ts[0])),
+		(*C.double)(unsafe.Pointer(&vals[0])),
+		(*C.uint32_t)(unsafe.Pointer(&counts[0])),
+		unitsPtr, startPtr, annPtr, C.uint32_t(annStride),
+		C.uint32_t(n), C.uint32_t(stride), intOpt, C.uint8_t(defaultUnit),
+		(*C.uint8_t)(unsafe.Pointer(&streams[0])), C.uint32_t(outStride),
+		(*C.uint32_t)(unsafe.Pointer(&lens[0])),
+		(*C.int32_t)(unsafe.Pointer(&errs[0])))
+	if rc != 0 {
+		return nil, nil, nil, lastError()
+	}
+	return streams, lens, errs, nil
+}

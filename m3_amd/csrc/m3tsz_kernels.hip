@@ -1201,8 +1201,65 @@ __device__ __forceinline__ int convert_to_int_float(double v, uint8_t cur_max_mu
     return 0;
 }
 
+/* XXH64, seed 0, from the published xxHash specification: the annotation
+ * dedupe checksum (timestamp_encoder.go:56,164-170). The bytes sit at any
+ * alignment inside an annotation region, hence the memcpy loads. */
+#define XXH_P1 11400714785074694791ULL
+#define XXH_P2 14029467366897019727ULL
+#define XXH_P3 1609587929392839161ULL
+#define XXH_P4 9650029242287828579ULL
+#define XXH_P5 2870177450012600261ULL
+#define XXH_EMPTY 0xEF46DB3751D8E999ULL /* XXH64 of the empty input */
+
+__device__ __forceinline__ uint64_t ld_le64(const uint8_t* p) {
+    uint64_t v; __builtin_memcpy(&v, p, 8); return v;
+}
+__device__ __forceinline__ uint32_t ld_le32(const uint8_t* p) {
+    uint32_t v; __builtin_memcpy(&v, p, 4); return v;
+}
+__device__ __forceinline__ uint64_t xxh_rotl(uint64_t x, uint32_t r) {
+    return (x << r) | (x >> (64 - r));
+}
+__device__ __forceinline__ uint64_t xxh_round(uint64_t acc, uint64_t in) {
+    return xxh_rotl(acc + in * XXH_P2, 31) * XXH_P1;
+}
+__device__ __forceinline__ uint64_t xxh_merge(uint64_t h, uint64_t v) {
+    return (h ^ xxh_round(0, v)) * XXH_P1 + XXH_P4;
+}
+__device__ __noinline__ uint64_t xxh64(const uint8_t* p, uint32_t len) {
+    const uint8_t* end = p + len;
+    uint64_t h;
+    if (len >= 32) {
+        uint64_t v1 = XXH_P1 + XXH_P2, v2 = XXH_P2, v3 = 0, v4 = 0 - XXH_P1;
+        do {
+            v1 = xxh_round(v1, ld_le64(p));
+            v2 = xxh_round(v2, ld_le64(p + 8));
+            v3 = xxh_round(v3, ld_le64(p + 16));
+            v4 = xxh_round(v4, ld_le64(p + 24));
+            p += 32;
+        } while (end - p >= 32);
+        h = xxh_rotl(v1, 1) + xxh_rotl(v2, 7) + xxh_rotl(v3, 12) + xxh_rotl(v4, 18);
+        h = xxh_merge(h, v1); h = xxh_merge(h, v2);
+        h = xxh_merge(h, v3); h = xxh_merge(h, v4);
+    } else {
+        h = XXH_P5;
+    }
+    h += len;
+    for (; end - p >= 8; p += 8)
+        h = xxh_rotl(h ^ xxh_round(0, ld_le64(p)), 27) * XXH_P1 + XXH_P4;
+    if (end - p >= 4) {
+        h = xxh_rotl(h ^ (uint64_t)ld_le32(p) * XXH_P1, 23) * XXH_P2 + XXH_P3;
+        p += 4;
+    }
+    for (; p < end; p++)
+        h = xxh_rotl(h ^ (uint64_t)*p * XXH_P5, 11) * XXH_P1;
+    h ^= h >> 33; h *= XXH_P2; h ^= h >> 29; h *= XXH_P3; h ^= h >> 32;
+    return h;
+}
+
 /* Encoder state: encoder.go:42-61 + TimestampEncoder + sig tracker. The bulk
- * path has a fixed unit and no annotations (m3gpu.h contract). */
+ * kernel drives it with one fixed unit through encode(); the full kernel
+ * passes each point's own unit and annotation through encode_full(). */
 struct Encoder {
     BitWriter w;
     int64_t unit_ns; /* cached UNIT_NS_D[unit] — the bulk path has one
@@ -1215,12 +1272,14 @@ struct Encoder {
     uint8_t num_sig_state, cur_highest_lower_sig, num_lower_sig;
     bool has_written_first, is_float, int_optimized;
     uint32_t num_encoded;
+    uint64_t prev_ann_checksum; /* encode_full only */
 
     __device__ __forceinline__ void init(uint8_t* row, uint32_t cap_bytes,
                          int64_t start_ns, bool intopt, uint8_t default_unit) {
         w.init(row, cap_bytes);
         prev_time = start_ns;
         prev_time_delta = 0;
+        prev_ann_checksum = XXH_EMPTY;
         prev_xor = 0; prev_float_bits = 0;
         int_val = 0;
         /* initialTimeUnit (timestamp_encoder.go:248-259) */
@@ -1281,7 +1340,27 @@ struct Encoder {
         return 0;
     }
 
-    /* timestamp_encoder.go:72-129 (fixed unit, no annotations) */
+    /* timestamp_encoder.go:161-195 shouldWriteAnnotation + writeAnnotation:
+     * marker, binary.PutVarint(len - 1), then the bytes at the current bit
+     * position, 8 at a time while 8 remain. Caller guarantees len > 0.
+     * Inlined, so that the encoder's address never leaves the kernel and its
+     * state stays in registers; only the checksum is a real call. */
+    __device__ __forceinline__ void write_annotation(const uint8_t* ant, uint32_t len) {
+        uint64_t checksum = xxh64(ant, len);
+        if (checksum == prev_ann_checksum) return;
+        write_marker(MARKER_ANNOTATION);
+        uint64_t ux = (uint64_t)(len - 1) << 1; /* zigzag of a value >= 0 */
+        for (; ux >= 0x80; ux >>= 7) w.write_bits((ux & 0x7f) | 0x80, 8);
+        w.write_bits(ux, 8);
+        uint32_t i = 0;
+        for (; len - i >= 8; i += 8)
+            w.write_bits(__builtin_bswap64(ld_le64(ant + i)), 64);
+        for (; i < len; i++) w.write_bits(ant[i], 8);
+        prev_ann_checksum = checksum;
+    }
+
+    /* timestamp_encoder.go:72-129; the annotation step of WriteNextTime
+     * (:104-106) is encode_full's */
     __device__ __forceinline__ int write_time(int64_t cur_time, uint8_t unit) {
         if (!has_written_first) {
             w.write_bits((uint64_t)prev_time, 64);
@@ -1469,6 +1548,18 @@ struct Encoder {
         return err ? err : w.err;
     }
 
+    /* encoder.go:90 Encode(dp, tu, ant). WriteTime's order: the start (first
+     * call only), the annotation, the unit change, the dod. */
+    __device__ __forceinline__ int encode_full(int64_t t, double v, uint8_t unit,
+                                               const uint8_t* ant, uint32_t ant_len) {
+        if (!has_written_first) {
+            w.write_bits((uint64_t)prev_time, 64);
+            has_written_first = true;
+        }
+        if (ant_len) write_annotation(ant, ant_len);
+        return encode(t, v, unit);
+    }
+
     /* Finalize: appending the EOS marker to the live bitstream produces
      * exactly head[:len-1] + Tail(lastByte, pos) (scheme.go:198-212). */
     __device__ __forceinline__ uint32_t finalize() {
@@ -1478,12 +1569,71 @@ struct Encoder {
     }
 };
 
+/* The optional per-series inputs of the full encode (m3gpu.h,
+ * m3gpu_encode_batch_full_dev); each pointer may be null. */
+struct EncodeFullIn {
+    const uint8_t* units;     /* [nseries*stride] per-point unit */
+    const int64_t* start_ns;  /* [nseries] block start */
+    const uint8_t* ann;       /* [nseries*ann_stride] annotation regions */
+    uint32_t ann_stride;      /* multiple of 4, >= 16 */
+};
+
+/* Walks one series' annotation region,
+ *   [u32 n_events][n_events x {u32 point, u32 off, u32 len}][...bytes],
+ * the layout k_decode_batch writes. init() checks the whole event table
+ * against the region and the point count before any annotation byte is
+ * read, so take() only ever addresses bytes inside the region. */
+struct AnnCursor {
+    const uint8_t* region;
+    uint32_t n_events, next_ev;
+    uint32_t next_pt; /* point of event next_ev; UINT32_MAX when exhausted */
+
+    __device__ __forceinline__ const uint32_t* event(uint32_t e) const {
+        return (const uint32_t*)(region + 4 + (uint64_t)e * 12);
+    }
+    __device__ __forceinline__ int init(const uint8_t* r, uint32_t ann_stride,
+                                        uint32_t count) {
+        region = r;
+        n_events = 0; next_ev = 0; next_pt = UINT32_MAX;
+        if (!r) return 0;
+        uint32_t n = *(const uint32_t*)r;
+        if (n > (ann_stride - 4) / 12) return M3GPU_SERIES_ANNOTATION;
+        uint32_t prev = 0;
+        for (uint32_t e = 0; e < n; e++) {
+            const uint32_t* ev = event(e);
+            uint32_t pt = ev[0], off = ev[1], len = ev[2];
+            if (pt >= count || (e && pt <= prev) ||
+                off > ann_stride || len > ann_stride - off)
+                return M3GPU_SERIES_ANNOTATION;
+            prev = pt;
+        }
+        n_events = n;
+        if (n) next_pt = event(0)[0];
+        return 0;
+    }
+    /* the event at next_pt: its bytes and length (0 = no annotation) */
+    __device__ __forceinline__ const uint8_t* take(uint32_t* len) {
+        const uint32_t* ev = event(next_ev);
+        const uint8_t* p = region + ev[1];
+        *len = ev[2];
+        next_ev++;
+        next_pt = next_ev < n_events ? event(next_ev)[0] : UINT32_MAX;
+        return p;
+    }
+};
+
+/* FULL = false is the bulk kernel: one fixed unit, start = first timestamp,
+ * no annotations; `in` is not touched. FULL = true is encoder.go:90
+ * Encode(dp, tu, ant) per point: per-point units, annotations and an explicit
+ * block start (timestamp_encoder.go:72-259); `unit` is the default unit. */
+template <bool FULL>
 __global__ void __launch_bounds__(BLOCK_THREADS)
 k_encode_batch(const int64_t* __restrict__ ts, const double* __restrict__ vals,
                const uint32_t* __restrict__ counts, uint32_t nseries,
                uint32_t stride, int int_optimized, uint8_t unit,
                uint8_t* __restrict__ out_bytes, uint32_t out_stride,
-               uint32_t* __restrict__ out_lens, int32_t* __restrict__ out_errs) {
+               uint32_t* __restrict__ out_lens, int32_t* __restrict__ out_errs,
+               EncodeFullIn in) {
     /* ONE SERIES PER LANE (like decode). Input points stage through an LDS
      * tile filled cooperatively — fill step j: lane l loads row (l>>3)+8j,
      * point (l&7): 8 consecutive 8B addresses per row = full 64B-line
@@ -1500,14 +1650,28 @@ k_encode_batch(const int64_t* __restrict__ ts, const double* __restrict__ vals,
     __shared__ double val_tile_all[WAVES_PER_BLOCK][WAVE][DEC_TILE];
     int64_t (*ts_tile)[DEC_TILE] = ts_tile_all[wave];
     double (*val_tile)[DEC_TILE] = val_tile_all[wave];
+    /* full kernel only (+2 KB/block): the tile's units, one byte per point,
+     * row r's 8 bytes at unit_tile[r] in point order, so each lane takes
+     * its tile's units with one 8-byte LDS read */
+    __shared__ uint64_t unit_tile_all[FULL ? WAVES_PER_BLOCK : 1][FULL ? WAVE : 1];
+    uint64_t* unit_tile = unit_tile_all[FULL ? wave : 0];
 
     const bool in_range = series < nseries;
     uint32_t n = in_range ? counts[series] : 0;
 
     Encoder e;
-    if (in_range)
+    AnnCursor ac;
+    int err = 0;
+    if (in_range) {
+        int64_t start = n ? ts[(uint64_t)series * stride] : 0;
+        if constexpr (FULL) {
+            if (in.start_ns) start = in.start_ns[series];
+            err = ac.init(in.ann ? in.ann + (uint64_t)series * in.ann_stride
+                                 : nullptr, in.ann_stride, n);
+        }
         e.init(out_bytes + (uint64_t)series * out_stride, out_stride,
-               n ? ts[(uint64_t)series * stride] : 0, int_optimized != 0, unit);
+               start, int_optimized != 0, unit);
+    }
 
     auto fill_tile = [&](uint32_t base_pt) {
         __builtin_amdgcn_wave_barrier();
@@ -1522,22 +1686,40 @@ k_encode_batch(const int64_t* __restrict__ ts, const double* __restrict__ vals,
                 uint32_t pc = p ^ (r & 7);
                 ts_tile[r][pc] = ts[row];
                 val_tile[r][pc] = vals[row];
+                if constexpr (FULL) {
+                    if (in.units)
+                        ((uint8_t*)&unit_tile[r])[p] = in.units[row];
+                }
             }
         }
         __builtin_amdgcn_wave_barrier();
     };
 
-    bool running = in_range && n > 0;
-    int err = 0;
+    bool running = in_range && n > 0 && !err;
     uint32_t len = 0;
     uint32_t j = 0;
+    uint64_t tile_units = 0;
     while (__any(running)) {
-        if ((j & (DEC_TILE - 1)) == 0) fill_tile(j);
+        if ((j & (DEC_TILE - 1)) == 0) {
+            fill_tile(j);
+            if constexpr (FULL) {
+                if (in.units) tile_units = unit_tile[lane];
+            }
+        }
         if (running) {
             uint32_t col = (j & (DEC_TILE - 1)) ^ (lane & 7);
             int64_t t = ts_tile[lane][col];
             double v = val_tile[lane][col];
-            err = e.encode(t, v, unit);
+            if constexpr (FULL) {
+                uint8_t u = in.units
+                    ? (uint8_t)(tile_units >> (8 * (j & (DEC_TILE - 1)))) : unit;
+                const uint8_t* ant = nullptr;
+                uint32_t ant_len = 0;
+                if (j == ac.next_pt) ant = ac.take(&ant_len);
+                err = e.encode_full(t, v, u, ant, ant_len);
+            } else {
+                err = e.encode(t, v, unit);
+            }
             if (err) {
                 running = false;
             } else if (j + 1 == n) {
@@ -2740,10 +2922,51 @@ int m3gpu_encode_batch_dev(
         return M3GPU_ERR_BADARG;
     }
     hipStream_t s = (hipStream_t)hip_stream;
-    hipLaunchKernelGGL(m3::k_encode_batch, dim3(grid_lane(nseries)),
+    hipLaunchKernelGGL(m3::k_encode_batch<false>, dim3(grid_lane(nseries)),
                        dim3(BLOCK_THREADS), 0, s,
                        d_ts, d_vals, d_counts, nseries, stride, int_optimized,
-                       unit, d_out_bytes, out_stride, d_out_lens, d_out_errs);
+                       unit, d_out_bytes, out_stride, d_out_lens, d_out_errs,
+                       m3::EncodeFullIn{});
+    HIP_TRY(hipGetLastError());
+    return M3GPU_OK;
+}
+
+/* argument rules of both full-encode forms; touches no HIP state */
+static int encode_full_check_args(bool has_ann, uint32_t ann_stride,
+                                  uint32_t out_stride) {
+    const char* msg = nullptr;
+    if (out_stride % 8)
+        msg = "out_stride must be a multiple of 8";
+    else if (has_ann && (ann_stride % 4 || ann_stride < 16))
+        msg = "ann_stride must be 4-byte aligned and >= 16";
+    else if (!has_ann && ann_stride)
+        msg = "ann_stride must be 0 without annotation regions";
+    if (!msg) return M3GPU_OK;
+    snprintf(g_err, sizeof(g_err), "%s", msg);
+    return M3GPU_ERR_BADARG;
+}
+
+int m3gpu_encode_batch_full_dev(
+    const int64_t* d_ts, const double* d_vals, const uint32_t* d_counts,
+    const uint8_t* d_units, const int64_t* d_start_ns,
+    const uint8_t* d_ann, uint32_t ann_stride,
+    uint32_t nseries, uint32_t stride, int int_optimized, uint8_t default_unit,
+    uint8_t* d_out_bytes, uint32_t out_stride, uint32_t* d_out_lens,
+    int32_t* d_out_errs, void* hip_stream) {
+    if (!nseries) return M3GPU_OK;
+    int rc = encode_full_check_args(d_ann != nullptr, ann_stride, out_stride);
+    if (rc != M3GPU_OK) return rc;
+    if ((uintptr_t)d_ann % 4) { /* the event tables are read as u32 */
+        snprintf(g_err, sizeof(g_err), "d_ann must be 4-byte aligned");
+        return M3GPU_ERR_BADARG;
+    }
+    hipStream_t s = (hipStream_t)hip_stream;
+    m3::EncodeFullIn in{d_units, d_start_ns, d_ann, ann_stride};
+    hipLaunchKernelGGL(m3::k_encode_batch<true>, dim3(grid_lane(nseries)),
+                       dim3(BLOCK_THREADS), 0, s,
+                       d_ts, d_vals, d_counts, nseries, stride, int_optimized,
+                       default_unit, d_out_bytes, out_stride, d_out_lens,
+                       d_out_errs, in);
     HIP_TRY(hipGetLastError());
     return M3GPU_OK;
 }
@@ -3028,33 +3251,72 @@ int m3gpu_decode_batch_ann(
                        ann_stride);
 }
 
-int m3gpu_encode_batch(
+/* Both encode forms: upload the points (and, for the full form, whichever
+ * optional inputs are given), encode on the null stream, copy the streams
+ * back. */
+static int encode_host(
     const int64_t* ts, const double* vals, const uint32_t* counts,
+    bool full, const uint8_t* units, const int64_t* start_ns,
+    const uint8_t* ann, uint32_t ann_stride,
     uint32_t nseries, uint32_t stride, int int_optimized, uint8_t unit,
     uint8_t* out_bytes, uint32_t out_stride, uint32_t* out_lens,
     int32_t* out_errs) {
-    DevBuf<int64_t> d_ts;
+    DevBuf<int64_t> d_ts, d_start;
     DevBuf<double> d_vals;
     DevBuf<uint32_t> d_counts, d_lens;
-    DevBuf<uint8_t> d_out;
+    DevBuf<uint8_t> d_out, d_units, d_ann;
     DevBuf<int32_t> d_errs;
     uint64_t npts = (uint64_t)nseries * stride;
     uint64_t outb = (uint64_t)nseries * out_stride;
     HIP_TRY(d_ts.upload(ts, npts));
     HIP_TRY(d_vals.upload(vals, npts));
     HIP_TRY(d_counts.upload(counts, nseries));
+    if (units) HIP_TRY(d_units.upload(units, npts));
+    if (start_ns) HIP_TRY(d_start.upload(start_ns, nseries));
+    if (ann) HIP_TRY(d_ann.upload(ann, (uint64_t)nseries * ann_stride));
     HIP_TRY(d_out.alloc(outb));
     HIP_TRY(hipMemset(d_out.p, 0, outb));
     HIP_TRY(d_lens.alloc(nseries));
     HIP_TRY(d_errs.alloc(nseries));
-    int rc = m3gpu_encode_batch_dev(d_ts.p, d_vals.p, d_counts.p, nseries,
-                                    stride, int_optimized, unit, d_out.p,
-                                    out_stride, d_lens.p, d_errs.p, nullptr);
+    int rc = full
+        ? m3gpu_encode_batch_full_dev(d_ts.p, d_vals.p, d_counts.p, d_units.p,
+                                      d_start.p, d_ann.p, ann_stride, nseries,
+                                      stride, int_optimized, unit, d_out.p,
+                                      out_stride, d_lens.p, d_errs.p, nullptr)
+        : m3gpu_encode_batch_dev(d_ts.p, d_vals.p, d_counts.p, nseries,
+                                 stride, int_optimized, unit, d_out.p,
+                                 out_stride, d_lens.p, d_errs.p, nullptr);
     if (rc != M3GPU_OK) return rc;
     HIP_TRY(d_out.download(out_bytes, outb));
     HIP_TRY(d_lens.download(out_lens, nseries));
     HIP_TRY(d_errs.download(out_errs, nseries));
     return M3GPU_OK;
+}
+
+int m3gpu_encode_batch(
+    const int64_t* ts, const double* vals, const uint32_t* counts,
+    uint32_t nseries, uint32_t stride, int int_optimized, uint8_t unit,
+    uint8_t* out_bytes, uint32_t out_stride, uint32_t* out_lens,
+    int32_t* out_errs) {
+    return encode_host(ts, vals, counts, false, nullptr, nullptr, nullptr, 0,
+                       nseries, stride, int_optimized, unit, out_bytes,
+                       out_stride, out_lens, out_errs);
+}
+
+/* what a cgo encoding.Encoder shim calls for batched Encode(dp, tu, ant) */
+int m3gpu_encode_batch_full(
+    const int64_t* ts, const double* vals, const uint32_t* counts,
+    const uint8_t* units, const int64_t* start_ns,
+    const uint8_t* ann, uint32_t ann_stride,
+    uint32_t nseries, uint32_t stride, int int_optimized, uint8_t default_unit,
+    uint8_t* out_bytes, uint32_t out_stride, uint32_t* out_lens,
+    int32_t* out_errs) {
+    int rc = encode_full_check_args(ann != nullptr, ann_stride, out_stride);
+    if (rc != M3GPU_OK) return rc;
+    return encode_host(ts, vals, counts, true, units, start_ns, ann,
+                       ann_stride, nseries, stride, int_optimized,
+                       default_unit, out_bytes, out_stride, out_lens,
+                       out_errs);
 }
 
 int m3gpu_rollup_batch(

@@ -79,6 +79,17 @@ def lib():
         L.m3gpu_encode_batch.restype = c_int
         L.m3gpu_encode_batch.argtypes = [P(c_i64), P(c_f64), P(c_u32), c_u32, c_u32,
                                          c_int, c_u8, P(c_u8), c_u32, P(c_u32), P(c_i32)]
+        L.m3gpu_encode_batch_full_dev.restype = c_int
+        L.m3gpu_encode_batch_full_dev.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                  c_vp, c_u32, c_u32, c_u32,
+                                                  c_int, c_u8, c_vp, c_u32,
+                                                  c_vp, c_vp, c_vp]
+        L.m3gpu_encode_batch_full.restype = c_int
+        L.m3gpu_encode_batch_full.argtypes = [P(c_i64), P(c_f64), P(c_u32),
+                                              P(c_u8), P(c_i64), P(c_u8),
+                                              c_u32, c_u32, c_u32, c_int, c_u8,
+                                              P(c_u8), c_u32, P(c_u32),
+                                              P(c_i32)]
         L.m3gpu_compact_dev.restype = c_int
         L.m3gpu_compact_dev.argtypes = [c_vp, c_u32, c_vp, c_vp, c_u32, c_vp, c_vp]
         L.m3gpu_rollup_batch_dev.restype = c_int
@@ -177,6 +188,51 @@ def encode_batch(ts, vals, counts, int_optimized=True, unit=1,
     return out_bytes, out_lens, out_errs
 
 
+def full_out_stride(stride, per_point_units=False, ann_bytes=0, ann_events=0):
+    """An out_stride that holds the worst-case full-encode stream of one
+    series (m3gpu.h): the bulk bound, 83 bits per possible unit change, and
+    per annotation 11 bits + up to 5 varint bytes + its bytes."""
+    n = 24 * stride + 32
+    if per_point_units:
+        n += 11 * stride
+    n += ann_bytes + 7 * ann_events
+    return (n + 15) & ~15
+
+
+def encode_batch_full(ts, vals, counts, units=None, start_ns=None, ann=None,
+                      int_optimized=True, default_unit=1, out_stride=None,
+                      check_errors=True):
+    """Host form of the full encode (Encoder.Encode(dp, tu, ant) batched).
+    units: uint8 [nseries, stride]; start_ns: int64 [nseries]; ann: uint8
+    [nseries, ann_stride] regions (build_ann_region); each may be None."""
+    ts = _np(ts, np.int64)
+    vals = _np(vals, np.float64)
+    counts = _np(counts, np.uint32)
+    nseries, stride = ts.shape
+    units = None if units is None else _np(units, np.uint8)
+    start_ns = None if start_ns is None else _np(start_ns, np.int64)
+    ann = None if ann is None else _np(ann, np.uint8)
+    ann_stride = 0 if ann is None else ann.shape[1]
+    if out_stride is None:
+        out_stride = full_out_stride(stride, units is not None, ann_stride,
+                                     ann_stride // 12)
+    out_bytes = np.zeros((nseries, out_stride), dtype=np.uint8)
+    out_lens = np.empty(nseries, dtype=np.uint32)
+    out_errs = np.empty(nseries, dtype=np.int32)
+    rc = lib().m3gpu_encode_batch_full(
+        _pp(ts, c_i64), _pp(vals, c_f64), _pp(counts, c_u32),
+        None if units is None else _pp(units, c_u8),
+        None if start_ns is None else _pp(start_ns, c_i64),
+        None if ann is None else _pp(ann, c_u8), ann_stride,
+        nseries, stride, 1 if int_optimized else 0, default_unit,
+        _pp(out_bytes, c_u8), out_stride, _pp(out_lens, c_u32),
+        _pp(out_errs, c_i32))
+    _check(rc, "m3gpu_encode_batch_full")
+    if check_errors:
+        _raise_series_errors(out_errs, "encode")
+    return out_bytes, out_lens, out_errs
+
+
 def rollup_batch(blob, offsets, lens, metric_type, window_ns, nbuckets,
                  agg_types, int_optimized=True, default_unit=1,
                  check_errors=True):
@@ -260,6 +316,40 @@ def parse_ann_region(region):
     return out
 
 
+def ann_region_size(events):
+    """Bytes a region needs for [(point_idx, bytes)] events, rounded to 4
+    (and at least the 16 the C ABI asks for)."""
+    n = 4 + sum(12 + len(b) for _, b in events)
+    return max(16, (n + 3) & ~3)
+
+
+def build_ann_region(events, ann_stride):
+    """Inverse of parse_ann_region: lay [(point_idx, bytes)] set-events out
+    as one series' annotation region of ann_stride bytes (host uint8 array),
+    event table from the head, bytes from the tail. Raises ValueError when
+    the events do not fit or their points are not strictly increasing."""
+    events = [(int(p), bytes(b)) for p, b in events]
+    if ann_stride % 4 or ann_stride < 16:
+        raise ValueError("ann_stride must be a multiple of 4 and >= 16")
+    if 4 + sum(12 + len(b) for _, b in events) > ann_stride:
+        raise ValueError(
+            f"{len(events)} annotation events do not fit ann_stride={ann_stride}")
+    region = np.zeros(ann_stride, dtype=np.uint8)
+    table = np.zeros(1 + 3 * len(events), dtype=np.uint32)
+    table[0] = len(events)
+    tail = ann_stride
+    prev = -1
+    for i, (point, b) in enumerate(events):
+        if point <= prev:
+            raise ValueError("annotation points must be strictly increasing")
+        prev = point
+        tail -= len(b)
+        region[tail:tail + len(b)] = np.frombuffer(b, dtype=np.uint8)
+        table[1 + 3 * i: 4 + 3 * i] = (point, tail, len(b))
+    region[:table.nbytes] = table.view(np.uint8)
+    return region
+
+
 def decoded_ann_per_point(region, npts):
     """Materialize the sticky PrevAnt view (iterator.go:226-231): the
     annotation returned with each of npts datapoints (None until the first
@@ -285,6 +375,28 @@ def encode_batch_dev(d_ts, d_vals, d_counts, out_bytes, out_lens, out_errs,
         1 if int_optimized else 0, unit, _dev_ptr(out_bytes), out_stride,
         _dev_ptr(out_lens), _dev_ptr(out_errs), _torch_stream())
     _check(rc, "m3gpu_encode_batch_dev")
+
+
+def encode_batch_full_dev(d_ts, d_vals, d_counts, out_bytes, out_lens,
+                          out_errs, d_units=None, d_start_ns=None, d_ann=None,
+                          int_optimized=True, default_unit=1):
+    """Full encode, Encoder.Encode(dp, tu, ant) batched (encoder.go:90).
+    Optional torch CUDA tensors: d_units uint8 [nseries, stride] (per-point
+    unit), d_start_ns int64 [nseries] (block start), d_ann uint8
+    [nseries, ann_stride] (regions in the decode_batch_dev_ann layout; see
+    build_ann_region). With all three None the output equals
+    encode_batch_dev's."""
+    nseries, stride = d_ts.shape
+    rc = lib().m3gpu_encode_batch_full_dev(
+        _dev_ptr(d_ts), _dev_ptr(d_vals), _dev_ptr(d_counts),
+        _dev_ptr(d_units) if d_units is not None else None,
+        _dev_ptr(d_start_ns) if d_start_ns is not None else None,
+        _dev_ptr(d_ann) if d_ann is not None else None,
+        d_ann.shape[1] if d_ann is not None else 0,
+        nseries, stride, 1 if int_optimized else 0, default_unit,
+        _dev_ptr(out_bytes), out_bytes.shape[1], _dev_ptr(out_lens),
+        _dev_ptr(out_errs), _torch_stream())
+    _check(rc, "m3gpu_encode_batch_full_dev")
 
 
 def compact_dev(d_src, src_stride, d_lens, d_dst_offsets, d_dst):
@@ -644,17 +756,11 @@ class CommitLog:
         return out
 
 
-def commitlog_bootstrap_dev(torch, path, int_optimized=True, device="cuda:0"):
-    """Bootstrap-from-commitlog on the GPU: parse + validate the log
-    (native reader), group per series, batch-encode every series into
-    M3TSZ blocks with the HIP encoder. Returns (series_meta, d_bytes,
-    d_lens, d_errs) where series_meta is the CommitLog.series() list.
-
-    Replaces the reference's commitlog bootstrapper read-and-re-encode
-    (bootstrap/bootstrapper/commitlog + series buffer encoders) with one
-    batched GPU encode."""
-    with CommitLog(path) as cl:
-        meta = cl.series()
+def _bootstrap_encode(torch, meta, int_optimized, device, lossless):
+    """Batch-encode CommitLog.series() dicts, one M3TSZ block per series.
+    lossless=False: the bulk encoder at the default unit, the log's units
+    and annotations dropped. lossless=True: the full encoder with each
+    point's logged unit and annotation."""
     if not meta:
         return [], None, None, None
     n = len(meta)
@@ -670,13 +776,51 @@ def commitlog_bootstrap_dev(torch, path, int_optimized=True, device="cuda:0"):
     d_ts = torch.from_numpy(ts).to(device)
     d_vals = torch.from_numpy(vals).to(device)
     d_counts = torch.from_numpy(counts).to(device)
-    out_stride = (24 * width + 32 + 15) & ~15
-    d_bytes = torch.zeros((n, out_stride), dtype=torch.uint8, device=device)
     d_lens = torch.empty(n, dtype=torch.int32, device=device)
     d_errs = torch.empty(n, dtype=torch.int32, device=device)
-    encode_batch_dev(d_ts, d_vals, d_counts, d_bytes, d_lens, d_errs,
-                     int_optimized=int_optimized)
+    if not lossless:
+        out_stride = (24 * width + 32 + 15) & ~15
+        d_bytes = torch.zeros((n, out_stride), dtype=torch.uint8, device=device)
+        encode_batch_dev(d_ts, d_vals, d_counts, d_bytes, d_lens, d_errs,
+                         int_optimized=int_optimized)
+        return meta, d_bytes, d_lens, d_errs
+    units = np.zeros((n, width), np.uint8)
+    for i, m in enumerate(meta):
+        units[i, :len(m["units"])] = m["units"]
+    # one annotation per point at most, which is what the encoder takes; an
+    # empty one is no annotation (shouldWriteAnnotation)
+    events = [[(p, b) for p, b in m["annotations"] if b] for m in meta]
+    d_ann = None
+    ann_bytes = ann_events = 0
+    if any(events):
+        ann_stride = max(ann_region_size(ev) for ev in events)
+        ann = np.stack([build_ann_region(ev, ann_stride) for ev in events])
+        d_ann = torch.from_numpy(ann).to(device)
+        ann_bytes = max(sum(len(b) for _, b in ev) for ev in events)
+        ann_events = max(len(ev) for ev in events)
+    out_stride = full_out_stride(width, True, ann_bytes, ann_events)
+    d_bytes = torch.zeros((n, out_stride), dtype=torch.uint8, device=device)
+    encode_batch_full_dev(d_ts, d_vals, d_counts, d_bytes, d_lens, d_errs,
+                          d_units=torch.from_numpy(units).to(device),
+                          d_ann=d_ann, int_optimized=int_optimized)
     return meta, d_bytes, d_lens, d_errs
+
+
+def commitlog_bootstrap_dev(torch, path, int_optimized=True, device="cuda:0",
+                            lossless=False):
+    """Bootstrap-from-commitlog on the GPU: parse + validate the log
+    (native reader), group per series, batch-encode every series into
+    M3TSZ blocks with the HIP encoder. Returns (series_meta, d_bytes,
+    d_lens, d_errs) where series_meta is the CommitLog.series() list.
+    lossless=True keeps each entry's time unit and annotation (the full
+    encoder); the default encodes every point at unit 1 without them.
+
+    Replaces the reference's commitlog bootstrapper read-and-re-encode
+    (bootstrap/bootstrapper/commitlog + series buffer encoders) with one
+    batched GPU encode."""
+    with CommitLog(path) as cl:
+        meta = cl.series()
+    return _bootstrap_encode(torch, meta, int_optimized, device, lossless)
 
 
 # ==================== unaggregated metric wire parser ====================
@@ -785,10 +929,10 @@ def commitlog_read_dir(dirpath):
                     order.append(key)
                 else:
                     g = merged[key]
+                    base = len(g["ts"])  # annotation points index the merged row
                     g["ts"] = np.concatenate([g["ts"], m["ts"]])
                     g["vals"] = np.concatenate([g["vals"], m["vals"]])
                     g["units"] = np.concatenate([g["units"], m["units"]])
-                    base = len(g["annotations"])
                     g["annotations"].extend(
                         (base + pi, b) for pi, b in m["annotations"])
         finally:
@@ -797,30 +941,10 @@ def commitlog_read_dir(dirpath):
 
 
 def commitlog_bootstrap_dir_dev(torch, dirpath, int_optimized=True,
-                                device="cuda:0"):
+                                device="cuda:0", lossless=False):
     """Bootstrap from a DIRECTORY of commit logs (the reference commitlog
     bootstrapper's whole-volume job): merge per series across files, then
-    batch-encode blocks with the HIP encoder."""
+    batch-encode blocks with the HIP encoder (lossless: as in
+    commitlog_bootstrap_dev)."""
     meta = commitlog_read_dir(dirpath)
-    if not meta:
-        return [], None, None, None
-    n = len(meta)
-    width = max(len(m["ts"]) for m in meta)
-    ts = np.zeros((n, width), np.int64)
-    vals = np.zeros((n, width), np.float64)
-    counts = np.zeros(n, np.int32)
-    for i, m in enumerate(meta):
-        k = len(m["ts"])
-        ts[i, :k] = m["ts"]
-        vals[i, :k] = m["vals"]
-        counts[i] = k
-    d_ts = torch.from_numpy(ts).to(device)
-    d_vals = torch.from_numpy(vals).to(device)
-    d_counts = torch.from_numpy(counts).to(device)
-    out_stride = (24 * width + 32 + 15) & ~15
-    d_bytes = torch.zeros((n, out_stride), dtype=torch.uint8, device=device)
-    d_lens = torch.empty(n, dtype=torch.int32, device=device)
-    d_errs = torch.empty(n, dtype=torch.int32, device=device)
-    encode_batch_dev(d_ts, d_vals, d_counts, d_bytes, d_lens, d_errs,
-                     int_optimized=int_optimized)
-    return meta, d_bytes, d_lens, d_errs
+    return _bootstrap_encode(torch, meta, int_optimized, device, lossless)
