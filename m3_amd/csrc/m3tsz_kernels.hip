@@ -13,8 +13,9 @@
  *      decode: each lane pulls its stream through a per-lane LDS word ring
  *        (topped up by deferred global loads, see BitReader) and stages 8
  *        decoded (ts, val) pairs in an LDS tile; the wave then flushes the
- *        tile transposed, 8 consecutive 8B stores per output row segment,
- *        which keeps write traffic at the algorithmic 16 B/pt.
+ *        tile transposed, 4 consecutive 16B stores per output row segment
+ *        (8 of 8B when the outputs are not 16-byte aligned), which keeps
+ *        write traffic at the algorithmic 16 B/pt.
  *      encode: each lane emits completed 64-bit words into its own row.
  *      rollup: the lane tier keeps per-bucket state in registers and small
  *        quantile buckets in a per-lane sorted LDS row; deep buckets retry
@@ -942,10 +943,14 @@ using RingDecoder = DecoderT<true>;  /* series-per-lane kernels: LDS ring */
  *    stream, commits them to its ring RF_SPAN points later, and the parser
  *    pulls words with ds_read_b64s.
  *  - OUTPUT staged in an LDS tile, [64 lanes][8 points] of (ts, val) pairs
- *    with an XOR column swizzle — one ds_write_b128 per point — and flushed
- *    every 8 points TRANSPOSED: lane l covers row (l>>3)+8j, point (l&7),
- *    so 8 lanes write one row's 64 contiguous bytes per array and
- *    WRITE_SIZE stays at the algorithmic 16 B/pt. */
+ *    with an XOR column swizzle (dec_swz) — one ds_write_b128 per point —
+ *    and flushed every 8 points TRANSPOSED, 16 bytes per lane and array:
+ *    lane l covers row (l>>2)+16j, j = 0..3, and the point pair 2*(l&3),
+ *    2*(l&3)+1, so 4 lanes write one row's 64 contiguous bytes per array,
+ *    a store instruction covers 16 rows, and WRITE_SIZE stays at the
+ *    algorithmic 16 B/pt. Outputs that are not 16-byte aligned, or an odd
+ *    stride, take the 8-byte form (row (l>>3)+8j, point l&7); the choice
+ *    is made once per launch. OUT_POLICY picks the stores' cache policy. */
 
 #define DEC_TILE 8
 /* points parsed between a ring top-up's issue and its commit; divides
@@ -955,10 +960,87 @@ using RingDecoder = DecoderT<true>;  /* series-per-lane kernels: LDS ring */
  * load, whose vmcnt(0) also drains the output stores. The span trades that
  * against how long a load has to land before its commit waits for it.
  * Same box, 1M x 1440 decode: span 8 16.1 ms, 4 15.9,
- * 2 14.5, 1 15.3. */
+ * 2 14.5, 1 15.3. Re-checked with the non-temporal 16-byte flush, where
+ * re-requested lines mostly hit the L2, RF_LOW / RF_SPAN one run each on
+ * one box: 3/2 14.04, 0/2 14.63, 0/4 15.46, 3/4 15.28 (under sc1 stores:
+ * 13.10, 13.75, 14.62, 14.39) — 3 and 2 stay. */
 #ifndef RF_SPAN
 #define RF_SPAN 2
 #endif
+
+/* Cache policy of the flush's output stores: 0 plain, 1 non-temporal (nt),
+ * 2 write-through (sc1). Plain and nt stores keep their line in the XCD's
+ * L2, where the 16 B/pt output stream competes with the lanes' open input
+ * lines; sc1 stores drop it. 1M x 1440 decode with the 16-byte flush, same
+ * box, alternated with the 8-byte plain parent (13.2-13.8 ms): plain
+ * 13.25-13.58, nt 12.76-13.09, sc1 13.11-13.43; `--data production`
+ * (parent 4.34-4.43): plain 4.44-4.46, nt 4.03-4.11, sc1 5.20 against a
+ * 4.95 parent. sc1 does what it says to the L2 — FETCH_SIZE 21.0 -> 9.6
+ * GB, hit rate 26% -> 46%, WRITE_SIZE unchanged — and moves no time: the
+ * kernel is not fabric-bound. nt is the default. */
+#ifndef OUT_POLICY
+#define OUT_POLICY 1
+#endif
+
+/* 1: 16 bytes per lane where alignment allows; 0: always the 8-byte form.
+ * With nt stores, same box: 8-byte 12.77-13.13 ms, 16-byte 12.76-13.09
+ * (a tie on the synthetic mix); `--data production` 4.24-4.27 against
+ * 4.03-4.11, where the 16-byte form wins. */
+#ifndef FLUSH_WIDE
+#define FLUSH_WIDE 1
+#endif
+
+typedef long long dec_ll2 __attribute__((ext_vector_type(2)));
+
+/* 8-byte output store. The sc1 form is the relaxed agent-scope atomic
+ * store: a global_store_dwordx2 sc1 that the compiler counts in vmcnt. */
+template <typename T>
+__device__ __forceinline__ void out_st8(T* p, long long x) {
+    static_assert(sizeof(T) == 8, "8-byte element");
+#if OUT_POLICY == 2
+    __hip_atomic_store((long long*)p, x, __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
+#elif OUT_POLICY == 1
+    __builtin_nontemporal_store(x, (long long*)p);
+#else
+    *(long long*)p = x;
+#endif
+}
+
+/* 16-byte output store of two consecutive elements; p is 16-byte aligned.
+ * No 16-byte atomic store exists, so the sc1 form is the instruction
+ * itself. The compiler does not count it in vmcnt, which only makes its
+ * own vmcnt(N) waits for counted loads stricter than needed (vmcnt retires
+ * in issue order), never laxer; nothing in the kernel reads the outputs
+ * back. The trailing s_nop keeps the next instruction from overwriting the
+ * data registers while the store still reads them. */
+template <typename T>
+__device__ __forceinline__ void out_st16(T* p, long long x0, long long x1) {
+    static_assert(sizeof(T) == 8, "8-byte element");
+    dec_ll2 v;
+    v.x = x0;
+    v.y = x1;
+#if OUT_POLICY == 2
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1"
+                 :: "v"(p), "v"(v));
+#elif OUT_POLICY == 1
+    __builtin_nontemporal_store(v, (dec_ll2*)p);
+#else
+    *(dec_ll2*)p = v;
+#endif
+}
+
+/* XOR column swizzle of the output tile for row r (0..7): r with its bits 0
+ * and 2 exchanged. A bijection of the row's low three bits keeps the 8
+ * lanes of a ds_write_b128 group on 8 different 16-byte columns; bit 0 from
+ * row bit 2 puts the four rows that one ds_read_b128 lane group of the wide
+ * flush touches ({0,3,5,6} or {1,2,4,7}, mod 8) on four different (row
+ * parity, column parity) classes; bit 2 independent of row bit 1 keeps the
+ * 8-byte flush's groups (rows {0,1,2,3} mod 4, half a row each)
+ * conflict-free as well. */
+__device__ __forceinline__ uint32_t dec_swz(uint32_t r) {
+    return ((r & 1) << 2) | (r & 2) | ((r >> 2) & 1);
+}
 
 __global__ void __launch_bounds__(BLOCK_THREADS, 4) /* hold the 128-VGPR
     granule: ring + tiles = 40 KB/block -> 4 blocks/CU, 4 waves/SIMD */
@@ -1001,40 +1083,78 @@ k_decode_batch(const uint8_t* __restrict__ blobs,
     uint32_t k = 0;
 
     const bool discard = out_ts == nullptr; /* parse-only diagnostic */
+    /* one decision per launch, wave-uniform (kernel arguments only): the
+     * 16-byte flush needs both arrays 16-byte aligned and an even stride */
+    const bool wide = FLUSH_WIDE && !discard && !(stride & 1) &&
+        !(((uintptr_t)out_ts | (uintptr_t)out_vals) & 15);
+    const uint32_t swz = dec_swz(lane & 7); /* this lane's OWN row, for step() */
 
-    /* transposed flush: lane l covers row (l>>3)+8j, point (l&7) — one
-     * ds_read_b128 pulls the (ts, val) pair, then two 8B stores whose
-     * addresses are consecutive across the 8 lanes of a row = full
-     * 64B-line utilization (WRITE_SIZE stays at the algorithmic 16 B/pt) */
-    auto flush = [&](uint32_t base_pt) {
-        if (discard) return;
-        __builtin_amdgcn_wave_barrier();
-        const uint32_t p = lane & (DEC_TILE - 1);
-        const uint32_t r0 = lane / DEC_TILE;
-        const uint32_t pt = base_pt + p;
+    /* transposed flush, wide form: lane l covers row (l>>2)+16j and the
+     * point pair 2*(l&3), 2*(l&3)+1 — two ds_read_b128 pull the two (ts,
+     * val) pairs, then one 16B store per array; the 4 lanes of a row write
+     * its 64 contiguous bytes = full 64B-line utilization (WRITE_SIZE stays
+     * at the algorithmic 16 B/pt). A partial row stores 16 bytes where both
+     * points of the pair exist, 8 where only the first does. */
+    auto flush_wide = [&](uint32_t base_pt) {
+        const uint32_t q = lane & 3;
+        const uint32_t r0 = lane >> 2;
+        const uint32_t pt = base_pt + 2 * q;
+        /* rows r0 + 16j share r0's low three bits, hence one swizzle */
+        const uint32_t pc = (2 * q) ^ dec_swz(r0 & 7);
         if (__all(cnt >= base_pt + DEC_TILE)) {
             /* all 64 rows full: unconditional stores, no per-row counts */
-            for (uint32_t j = 0; j < DEC_TILE; j++) {
-                uint32_t rr = r0 + j * (WAVE / DEC_TILE);
-                uint32_t pc = p ^ (rr & 7);
+            for (uint32_t j = 0; j < DEC_TILE / 2; j++) {
+                uint32_t rr = r0 + j * (WAVE / 4);
                 uint64_t row = (uint64_t)__shfl((int)series, (int)rr);
-                longlong2 pr = tile[rr][pc];
-                out_ts[row * stride + pt] = pr.x;
-                out_vals[row * stride + pt] = __longlong_as_double(pr.y);
+                longlong2 p0 = tile[rr][pc];
+                longlong2 p1 = tile[rr][pc ^ 1];
+                out_st16(out_ts + row * stride + pt, p0.x, p1.x);
+                out_st16(out_vals + row * stride + pt, p0.y, p1.y);
             }
         } else {
-            for (uint32_t j = 0; j < DEC_TILE; j++) {
-                uint32_t rr = r0 + j * (WAVE / DEC_TILE);
-                uint32_t pc = p ^ (rr & 7);
+            for (uint32_t j = 0; j < DEC_TILE / 2; j++) {
+                uint32_t rr = r0 + j * (WAVE / 4);
                 uint32_t cc = (uint32_t)__shfl((int)cnt, (int)rr);
                 uint64_t row = (uint64_t)__shfl((int)series, (int)rr);
                 if (pt < cc) {
-                    longlong2 pr = tile[rr][pc];
-                    out_ts[row * stride + pt] = pr.x;
-                    out_vals[row * stride + pt] = __longlong_as_double(pr.y);
+                    longlong2 p0 = tile[rr][pc];
+                    if (pt + 1 < cc) {
+                        longlong2 p1 = tile[rr][pc ^ 1];
+                        out_st16(out_ts + row * stride + pt, p0.x, p1.x);
+                        out_st16(out_vals + row * stride + pt, p0.y, p1.y);
+                    } else {
+                        out_st8(out_ts + row * stride + pt, p0.x);
+                        out_st8(out_vals + row * stride + pt, p0.y);
+                    }
                 }
             }
         }
+    };
+    /* 8-byte form, for outputs that are not 16-byte aligned or an odd
+     * stride: lane l covers row (l>>3)+8j, point (l&7) — one ds_read_b128,
+     * then two 8B stores consecutive across the 8 lanes of a row */
+    auto flush_narrow = [&](uint32_t base_pt) {
+        const uint32_t p = lane & (DEC_TILE - 1);
+        const uint32_t r0 = lane / DEC_TILE;
+        const uint32_t pt = base_pt + p;
+        const uint32_t pc = p ^ dec_swz(r0 & 7); /* rows r0 + 8j: same swizzle */
+        const bool full = __all(cnt >= base_pt + DEC_TILE);
+        for (uint32_t j = 0; j < DEC_TILE; j++) {
+            uint32_t rr = r0 + j * (WAVE / DEC_TILE);
+            uint32_t cc = (uint32_t)__shfl((int)cnt, (int)rr);
+            uint64_t row = (uint64_t)__shfl((int)series, (int)rr);
+            if (full || pt < cc) {
+                longlong2 pr = tile[rr][pc];
+                out_st8(out_ts + row * stride + pt, pr.x);
+                out_st8(out_vals + row * stride + pt, pr.y);
+            }
+        }
+    };
+    auto flush = [&](uint32_t base_pt) {
+        if (discard) return;
+        __builtin_amdgcn_wave_barrier();
+        if (wide) flush_wide(base_pt);
+        else flush_narrow(base_pt);
         __builtin_amdgcn_wave_barrier();
     };
 
@@ -1053,7 +1173,7 @@ k_decode_batch(const uint8_t* __restrict__ blobs,
                 running = false;
             } else {
                 if (!discard) {
-                    uint32_t col = j ^ (lane & 7);
+                    uint32_t col = j ^ swz;
                     longlong2 pr;
                     pr.x = t;
                     pr.y = __double_as_longlong(v);
