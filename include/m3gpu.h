@@ -128,6 +128,54 @@ int m3gpu_decode_batch(
     int64_t* out_ts, double* out_vals, uint32_t* out_counts,
     int32_t* out_errs, uint32_t stride);
 
+/* Full decode: the batched form of ReaderIterator.Current(), which returns
+ * (datapoint, unit, annotation) (iterator.go:221-231), plus the block start.
+ * Streams, d_perm, points, counts and errs are as in
+ * m3gpu_decode_batch_dev_perm; three optional outputs are added, each of
+ * which may be NULL (skipped):
+ *  - d_out_units [nseries*stride]: d_out_units[i*stride + p] is the time
+ *    unit in force after point p of series i was read, the unit Current()
+ *    reports with it. Written for exactly the points whose ts/vals are
+ *    written (p < d_out_counts[i], hence p < stride); no other byte of the
+ *    array is touched. A plain byte array: any base address and any stride,
+ *    odd ones included.
+ *  - d_out_start_ns [nseries]: the first 64 bits of the stream, the block
+ *    start (usually not the first timestamp). 0 for a stream whose first 64
+ *    bits cannot be read: an empty one, or one that ends before them.
+ *  - d_out_ann: one region of ann_stride bytes per series, written as by
+ *    m3gpu_decode_batch_dev_ann (4-byte aligned, ann_stride a multiple of 4
+ *    and >= 16). NULL (with ann_stride 0): annotations are skipped.
+ * With all three NULL, ts, vals, counts and errs equal
+ * m3gpu_decode_batch_dev_perm's.
+ * (d_out_ts, d_out_vals, d_out_counts, d_out_units, d_out_start_ns,
+ * d_out_ann) can be passed unchanged to m3gpu_encode_batch_full_dev with the
+ * same default_unit and int_optimized; for any stream the reference encoder
+ * wrote, that reproduces the stream byte for byte.
+ * M3GPU_ERR_BADARG, before any work is queued: d_out_ann given with
+ * ann_stride % 4 != 0 or ann_stride < 16, or itself not 4-byte aligned;
+ * d_out_ann NULL with ann_stride != 0. */
+int m3gpu_decode_batch_full_dev(
+    const uint8_t* d_blobs, const uint64_t* d_offsets, const uint32_t* d_lens,
+    const int32_t* d_perm,            /* NULL => identity schedule          */
+    uint32_t nseries, int int_optimized, uint8_t default_unit,
+    int64_t* d_out_ts, double* d_out_vals, uint32_t* d_out_counts,
+    int32_t* d_out_errs, uint32_t stride,
+    uint8_t* d_out_units,             /* [nseries*stride], NULL => skip     */
+    int64_t* d_out_start_ns,          /* [nseries], NULL => skip            */
+    uint8_t* d_out_ann, uint32_t ann_stride, /* NULL,0 => skip              */
+    void* hip_stream);
+
+/* host-pointer convenience form of the full decode. out_units comes back 0
+ * past each series' count, out_ann zero-filled outside what was written. */
+int m3gpu_decode_batch_full(
+    const uint8_t* blobs, uint64_t blobs_len,
+    const uint64_t* offsets, const uint32_t* lens,
+    uint32_t nseries, int int_optimized, uint8_t default_unit,
+    int64_t* out_ts, double* out_vals, uint32_t* out_counts,
+    int32_t* out_errs, uint32_t stride,
+    uint8_t* out_units, int64_t* out_start_ns,
+    uint8_t* out_ann, uint32_t ann_stride);
+
 /* -------- batched encode (replaces m3tsz.Encoder bulk writes:
  * src/dbnode/encoding/m3tsz/encoder.go:89-250) --------
  * Series i encodes counts[i] points from ts/vals rows (stride elements per
@@ -247,6 +295,20 @@ int m3gpu_merge_batch_dev(
     uint32_t nreplicas, uint32_t nseries, uint32_t stride,
     int64_t* d_out_ts, double* d_out_vals, uint32_t* d_out_counts,
     int32_t* d_out_errs, uint32_t out_stride, void* hip_stream);
+
+/* The same merge, carrying MultiReaderIterator.Current()'s unit: d_units
+ * rows are laid out like the d_ts rows (replica-major, stride bytes per
+ * row, e.g. m3gpu_decode_batch_full_dev's d_out_units), d_out_units has
+ * out_stride bytes per series. Each emitted point gets the unit of the
+ * replica whose value it got (iterators.go current()). Both unit pointers
+ * are required; ts, vals, counts and errs equal m3gpu_merge_batch_dev's.
+ * Annotations are not carried. */
+int m3gpu_merge_batch_units_dev(
+    const int64_t* d_ts, const double* d_vals, const uint8_t* d_units,
+    const uint32_t* d_counts, uint32_t nreplicas, uint32_t nseries,
+    uint32_t stride, int64_t* d_out_ts, double* d_out_vals,
+    uint8_t* d_out_units, uint32_t* d_out_counts, int32_t* d_out_errs,
+    uint32_t out_stride, void* hip_stream);
 
 int m3gpu_rollup_batch(
     const uint8_t* blobs, uint64_t blobs_len,

@@ -227,6 +227,131 @@ func DecodeBatchAnn(
 	return ts, vals, counts, errs, anns, nil
 }
 
+// FullDecoded is what DecodeBatchFull returns: DecodeBatch's rows plus, per
+// point, the time unit ReaderIterator.Current() reports with it, per series
+// the block start (the stream's first 64 bits) and the annotation-set
+// events. Ts, Vals, Counts, Units, StartNs and Anns can be passed unchanged
+// to EncodeBatchFull, which reproduces the streams.
+type FullDecoded struct {
+	Ts      []int64
+	Vals    []float64
+	Units   []byte // len n*stride, 0 past each series' count
+	Counts  []uint32
+	Errs    []SeriesError
+	StartNs []int64
+	Anns    [][]AnnotationEvent // nil when annStride == 0
+}
+
+// DecodeBatchFull is the batched form of ReaderIterator.Current()'s full
+// return, (datapoint, unit, annotation), plus the block start
+// (m3gpu_decode_batch_full). annStride == 0 skips the annotations; otherwise
+// it sizes the per-series region (4-aligned, >= 16) as in DecodeBatchAnn.
+// The device wrote the region headers: each is checked against annStride
+// before anything is sliced by it.
+func DecodeBatchFull(
+	blobs []byte, offsets []uint64, lens []uint32,
+	intOptimized bool, defaultUnit byte, stride uint32, annStride uint32,
+) (*FullDecoded, error) {
+	n := uint32(len(lens))
+	if n == 0 {
+		return &FullDecoded{}, nil
+	}
+	if len(blobs) == 0 || uint32(len(offsets)) < n+1 {
+		return nil, errors.New("m3gpu: need blobs and n+1 offsets")
+	}
+	if annStride != 0 && (annStride%4 != 0 || annStride < 16) {
+		return nil, errors.New("m3gpu: annStride must be 4-aligned and >= 16")
+	}
+	if stride == 0 {
+		return nil, errors.New("m3gpu: stride must be > 0")
+	}
+	npts := uint64(n) * uint64(stride)
+	d := &FullDecoded{
+		Ts:      make([]int64, npts),
+		Vals:    make([]float64, npts),
+		Units:   make([]byte, npts),
+		Counts:  make([]uint32, n),
+		Errs:    make([]SeriesError, n),
+		StartNs: make([]int64, n),
+	}
+	var region []byte
+	var annPtr *C.uint8_t
+	if annStride != 0 {
+		region = make([]byte, uint64(n)*uint64(annStride))
+		annPtr = (*C.uint8_t)(unsafe.Pointer(&region[0]))
+	}
+	intOpt := C.int(0)
+	if intOptimized {
+		intOpt = 1
+	}
+	rc := C.m3gpu_decode_batch_full(
+		(*C.uint8_t)(unsafe.Pointer(&blobs[0])), C.uint64_t(len(blobs)),
+		(*C.uint64_t)(unsafe.Pointer(&offsets[0])),
+		(*C.uint32_t)(unsafe.Pointer(&lens[0])),
+		C.uint32_t(n), intOpt, C.uint8_t(defaultUnit),
+		(*C.int64_t)(unsafe.Pointer(&d.Ts[0])),
+		(*C.double)(unsafe.Pointer(&d.Vals[0])),
+		(*C.uint32_t)(unsafe.Pointer(&d.Counts[0])),
+		(*C.int32_t)(unsafe.Pointer(&d.Errs[0])), C.uint32_t(stride),
+		(*C.uint8_t)(unsafe.Pointer(&d.Units[0])),
+		(*C.int64_t)(unsafe.Pointer(&d.StartNs[0])),
+		annPtr, C.uint32_t(annStride))
+	if rc != 0 {
+		return nil, lastError()
+	}
+	if annStride == 0 {
+		return d, nil
+	}
+	d.Anns = make([][]AnnotationEvent, n)
+	le := binary.LittleEndian
+	for i := uint32(0); i < n; i++ {
+		r := region[uint64(i)*uint64(annStride) : uint64(i+1)*uint64(annStride)]
+		nev := le.Uint32(r[0:4])
+		if nev > (annStride-4)/12 {
+			return nil, errors.New("m3gpu: annotation region: event count beyond the region")
+		}
+		evs := make([]AnnotationEvent, 0, nev)
+		for j := uint32(0); j < nev; j++ {
+			ev := r[4+j*12 : 4+j*12+12]
+			off, ln := le.Uint32(ev[4:8]), le.Uint32(ev[8:12])
+			if uint64(off)+uint64(ln) > uint64(annStride) {
+				return nil, errors.New("m3gpu: annotation region: event bytes beyond the region")
+			}
+			evs = append(evs, AnnotationEvent{
+				Point: le.Uint32(ev[0:4]),
+				Bytes: append([]byte(nil), r[off:off+ln]...),
+			})
+		}
+		d.Anns[i] = evs
+	}
+	return d, nil
+}
+
+// MergeBatchUnits is the replica-deduplicating merge that also carries
+// MultiReaderIterator.Current()'s unit (m3gpu_merge_batch_units_dev). Like
+// the C entry it works on DEVICE buffers: dTs/dVals/dUnits hold
+// nreplicas*nseries rows of stride points (replica-major), dCounts their
+// counts; the outputs hold nseries rows of outStride points. Every emitted
+// point gets the unit of the replica whose value it got. The work is
+// enqueued on hipStream (nil: the null stream); the caller synchronizes.
+func MergeBatchUnits(
+	dTs, dVals, dUnits, dCounts unsafe.Pointer,
+	nreplicas, nseries, stride uint32,
+	dOutTs, dOutVals, dOutUnits, dOutCounts, dOutErrs unsafe.Pointer,
+	outStride uint32, hipStream unsafe.Pointer,
+) error {
+	rc := C.m3gpu_merge_batch_units_dev(
+		(*C.int64_t)(dTs), (*C.double)(dVals), (*C.uint8_t)(dUnits),
+		(*C.uint32_t)(dCounts), C.uint32_t(nreplicas), C.uint32_t(nseries),
+		C.uint32_t(stride), (*C.int64_t)(dOutTs), (*C.double)(dOutVals),
+		(*C.uint8_t)(dOutUnits), (*C.uint32_t)(dOutCounts),
+		(*C.int32_t)(dOutErrs), C.uint32_t(outStride), hipStream)
+	if rc != 0 {
+		return lastError()
+	}
+	return nil
+}
+
 // annRegionSize is the bytes one series' events need in an annotation
 // region: the event count, one 12-byte table entry per event, the bytes.
 func annRegionSize(evs []AnnotationEvent) uint64 {

@@ -350,6 +350,15 @@ struct DecoderT {
     uint32_t ann_stride_, ann_events, ann_tail, points;
     int ann_err;
 
+    /* The block start: the stream's first 64 bits, what read_first_timestamp
+     * reads into `nt`; 0 for a stream of `len` < 8 bytes, whose read fails
+     * with EOF. Re-read from the stream (the words of a stream of 8 bytes or
+     * more are addressable) instead of carried in registers through the
+     * point loop: one load per series, for the full decode's epilogue. */
+    __device__ __forceinline__ int64_t start_ns(uint32_t len) const {
+        return len >= 8 ? (int64_t)__builtin_bswap64(r.words[0]) : 0;
+    }
+
     __device__ __forceinline__ void init(const uint8_t* base, uint64_t off, uint32_t len,
                          bool intopt, uint8_t dunit, uint64_t* ring = nullptr,
                          uint8_t* ann = nullptr, uint32_t ann_stride = 0) {
@@ -1042,6 +1051,19 @@ __device__ __forceinline__ uint32_t dec_swz(uint32_t r) {
     return ((r & 1) << 2) | (r & 2) | ((r >> 2) & 1);
 }
 
+/* The optional per-series outputs of the full decode (m3gpu.h,
+ * m3gpu_decode_batch_full_dev); each pointer may be null. */
+struct DecodeFullOut {
+    uint8_t* units;     /* [nseries*stride] per-point unit, any alignment */
+    int64_t* start_ns;  /* [nseries] block start */
+};
+
+/* FULL = false is the bulk kernel; `full` is not touched. FULL = true also
+ * returns ReaderIterator.Current()'s unit for every stored point and the
+ * stream's first 64 bits. The units take no LDS (the 40 KB of ring + tile
+ * already fill a CU's 160 KB four times): a lane packs its own 8 unit bytes
+ * of the tile into one 64-bit register and stores its own row at the flush. */
+template <bool FULL>
 __global__ void __launch_bounds__(BLOCK_THREADS, 4) /* hold the 128-VGPR
     granule: ring + tiles = 40 KB/block -> 4 blocks/CU, 4 waves/SIMD */
 k_decode_batch(const uint8_t* __restrict__ blobs,
@@ -1052,7 +1074,8 @@ k_decode_batch(const uint8_t* __restrict__ blobs,
                int64_t* __restrict__ out_ts, double* __restrict__ out_vals,
                uint32_t* __restrict__ out_counts, int32_t* __restrict__ out_errs,
                uint32_t stride,
-               uint8_t* __restrict__ out_ann, uint32_t ann_stride) {
+               uint8_t* __restrict__ out_ann, uint32_t ann_stride,
+               DecodeFullOut full) {
     const uint32_t lane = threadIdx.x & (WAVE - 1);
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t slot = blockIdx.x * BLOCK_THREADS + wave * WAVE + lane;
@@ -1158,6 +1181,24 @@ k_decode_batch(const uint8_t* __restrict__ blobs,
         __builtin_amdgcn_wave_barrier();
     };
 
+    /* full kernel: byte j of tile_units is the unit after this tile's point
+     * j. Each lane stores its own row's bytes, exactly those of the points
+     * the flush stores (base_pt <= p < cnt, and cnt <= stride): one 8-byte
+     * store for a full tile at an 8-byte aligned address, byte stores
+     * otherwise. Registers only, so no barrier and no tile. */
+    uint64_t tile_units = 0;
+    auto flush_units = [&](uint32_t base_pt) {
+        if (!full.units || cnt <= base_pt) return;
+        const uint32_t nb = min(cnt - base_pt, (uint32_t)DEC_TILE);
+        uint8_t* p = full.units + (uint64_t)series * stride + base_pt;
+        if (nb == DEC_TILE && !((uintptr_t)p & 7)) {
+            *(uint64_t*)p = tile_units;
+        } else {
+            for (uint32_t i = 0; i < nb; i++)
+                p[i] = (uint8_t)(tile_units >> (8 * i));
+        }
+    };
+
     /* capacity is tile-hoisted: the per-point check only runs on the rare
      * tile that could cross `stride` */
     auto step = [&](uint32_t j, bool check_cap) {
@@ -1179,6 +1220,8 @@ k_decode_batch(const uint8_t* __restrict__ blobs,
                     pr.y = __double_as_longlong(v);
                     tile[lane][col] = pr;
                 }
+                if constexpr (FULL)
+                    tile_units |= (uint64_t)d.time_unit << (8 * j);
                 cnt++;
             }
         }
@@ -1205,6 +1248,10 @@ k_decode_batch(const uint8_t* __restrict__ blobs,
             d.r.refill_commit(pd);
         }
         flush(k);
+        if constexpr (FULL) {
+            flush_units(k);
+            tile_units = 0;
+        }
         k += DEC_TILE;
     }
 
@@ -1212,6 +1259,10 @@ k_decode_batch(const uint8_t* __restrict__ blobs,
         d.ann_finish(&err);
         out_counts[series] = cnt;
         out_errs[series] = err;
+        if constexpr (FULL) {
+            if (full.start_ns)
+                full.start_ns[series] = d.start_ns(lens[series]);
+        }
     }
 }
 
@@ -2413,13 +2464,19 @@ k_count_errcode(const int32_t* __restrict__ errs, uint32_t n, int32_t code,
 #define MERGE_MAX_R 4
 #define MERGE_ERR_OUT_OF_ORDER 100
 
+/* UNITS = true also carries each point's time unit: `units` rows are laid
+ * out like the ts rows, a byte per point, and an emitted point gets the unit
+ * of the replica whose value it got (iterators.go current()). UNITS = false
+ * touches neither pointer. */
+template <bool UNITS>
 __global__ void __launch_bounds__(BLOCK_THREADS)
 k_merge(const int64_t* __restrict__ ts, const double* __restrict__ vals,
         const uint32_t* __restrict__ counts, uint32_t nreplicas,
         uint32_t nseries, uint32_t stride,
         int64_t* __restrict__ out_ts, double* __restrict__ out_vals,
         uint32_t* __restrict__ out_counts, int32_t* __restrict__ out_errs,
-        uint32_t out_stride) {
+        uint32_t out_stride,
+        const uint8_t* __restrict__ units, uint8_t* __restrict__ out_units) {
     const uint32_t series = blockIdx.x * BLOCK_THREADS + threadIdx.x;
     if (series >= nseries) return;
 
@@ -2429,6 +2486,8 @@ k_merge(const int64_t* __restrict__ ts, const double* __restrict__ vals,
     uint32_t cur[MERGE_MAX_R];
     int64_t cur_ts[MERGE_MAX_R];
     double cur_val[MERGE_MAX_R];
+    const uint8_t* ur[MERGE_MAX_R];
+    uint8_t cur_unit[MERGE_MAX_R];
 
     uint32_t ord = 0; /* packed replica ids, byte per slot, slot 0 = lowest */
     uint32_t nvals = 0;
@@ -2442,6 +2501,10 @@ k_merge(const int64_t* __restrict__ ts, const double* __restrict__ vals,
             if (cnt[r] > 0) {
                 cur_ts[r] = tr[r][0];
                 cur_val[r] = vr[r][0];
+                if constexpr (UNITS) {
+                    ur[r] = units + ((uint64_t)r * nseries + series) * stride;
+                    cur_unit[r] = ur[r][0];
+                }
                 ord |= r << (8 * nvals);
                 nvals++;
             }
@@ -2475,6 +2538,8 @@ k_merge(const int64_t* __restrict__ ts, const double* __restrict__ vals,
             if (n >= out_stride) { err = M3GPU_SERIES_CAPACITY; break; }
             orow_ts[n] = earliest;
             orow_val[n] = cur_val[winner];
+            if constexpr (UNITS)
+                out_units[(uint64_t)series * out_stride + n] = cur_unit[winner];
             n++;
             prev_at = earliest;
             first = false;
@@ -2494,6 +2559,7 @@ k_merge(const int64_t* __restrict__ ts, const double* __restrict__ vals,
                 }
                 cur_ts[r] = tr[r][cur[r]];
                 cur_val[r] = vr[r][cur[r]];
+                if constexpr (UNITS) cur_unit[r] = ur[r][cur[r]];
             }
             i++;
         }
@@ -2999,11 +3065,51 @@ int m3gpu_decode_batch_dev_perm(
     int32_t* d_out_errs, uint32_t stride, void* hip_stream) {
     if (!nseries) return M3GPU_OK;
     hipStream_t s = (hipStream_t)hip_stream;
-    hipLaunchKernelGGL(m3::k_decode_batch, dim3(grid_lane(nseries)),
+    hipLaunchKernelGGL(m3::k_decode_batch<false>, dim3(grid_lane(nseries)),
                        dim3(BLOCK_THREADS), 0, s,
                        d_blobs, d_offsets, d_lens, d_perm, nseries,
                        int_optimized, default_unit, d_out_ts, d_out_vals,
-                       d_out_counts, d_out_errs, stride, (uint8_t*)NULL, 0);
+                       d_out_counts, d_out_errs, stride, (uint8_t*)NULL, 0,
+                       m3::DecodeFullOut{});
+    HIP_TRY(hipGetLastError());
+    return M3GPU_OK;
+}
+
+/* annotation-region rules of both full-decode forms; touches no HIP state */
+static int decode_full_check_args(bool has_ann, uint32_t ann_stride) {
+    const char* msg = nullptr;
+    if (has_ann && (ann_stride % 4 || ann_stride < 16))
+        msg = "ann_stride must be 4-byte aligned and >= 16";
+    else if (!has_ann && ann_stride)
+        msg = "ann_stride must be 0 without annotation regions";
+    if (!msg) return M3GPU_OK;
+    snprintf(g_err, sizeof(g_err), "%s", msg);
+    return M3GPU_ERR_BADARG;
+}
+
+int m3gpu_decode_batch_full_dev(
+    const uint8_t* d_blobs, const uint64_t* d_offsets, const uint32_t* d_lens,
+    const int32_t* d_perm,
+    uint32_t nseries, int int_optimized, uint8_t default_unit,
+    int64_t* d_out_ts, double* d_out_vals, uint32_t* d_out_counts,
+    int32_t* d_out_errs, uint32_t stride,
+    uint8_t* d_out_units, int64_t* d_out_start_ns,
+    uint8_t* d_out_ann, uint32_t ann_stride, void* hip_stream) {
+    if (!nseries) return M3GPU_OK;
+    int rc = decode_full_check_args(d_out_ann != nullptr, ann_stride);
+    if (rc != M3GPU_OK) return rc;
+    if ((uintptr_t)d_out_ann % 4) { /* the event tables are written as u32 */
+        snprintf(g_err, sizeof(g_err), "d_out_ann must be 4-byte aligned");
+        return M3GPU_ERR_BADARG;
+    }
+    hipStream_t s = (hipStream_t)hip_stream;
+    m3::DecodeFullOut full{d_out_units, d_out_start_ns};
+    hipLaunchKernelGGL(m3::k_decode_batch<true>, dim3(grid_lane(nseries)),
+                       dim3(BLOCK_THREADS), 0, s,
+                       d_blobs, d_offsets, d_lens, d_perm, nseries,
+                       int_optimized, default_unit, d_out_ts, d_out_vals,
+                       d_out_counts, d_out_errs, stride, d_out_ann, ann_stride,
+                       full);
     HIP_TRY(hipGetLastError());
     return M3GPU_OK;
 }
@@ -3021,12 +3127,12 @@ int m3gpu_decode_batch_dev_ann(
         return M3GPU_ERR_BADARG;
     }
     hipStream_t s = (hipStream_t)hip_stream;
-    hipLaunchKernelGGL(m3::k_decode_batch, dim3(grid_lane(nseries)),
+    hipLaunchKernelGGL(m3::k_decode_batch<false>, dim3(grid_lane(nseries)),
                        dim3(BLOCK_THREADS), 0, s,
                        d_blobs, d_offsets, d_lens, (const int32_t*)NULL,
                        nseries, int_optimized, default_unit, d_out_ts,
                        d_out_vals, d_out_counts, d_out_errs, stride,
-                       d_out_ann, ann_stride);
+                       d_out_ann, ann_stride, m3::DecodeFullOut{});
     HIP_TRY(hipGetLastError());
     return M3GPU_OK;
 }
@@ -3290,11 +3396,36 @@ int m3gpu_merge_batch_dev(
         return M3GPU_ERR_BADARG;
     }
     hipStream_t s = (hipStream_t)hip_stream;
-    hipLaunchKernelGGL(m3::k_merge, dim3(grid_lane(nseries)),
+    hipLaunchKernelGGL(m3::k_merge<false>, dim3(grid_lane(nseries)),
                        dim3(BLOCK_THREADS), 0, s,
                        d_ts, d_vals, d_counts, nreplicas, nseries, stride,
                        d_out_ts, d_out_vals, d_out_counts, d_out_errs,
-                       out_stride);
+                       out_stride, (const uint8_t*)NULL, (uint8_t*)NULL);
+    HIP_TRY(hipGetLastError());
+    return M3GPU_OK;
+}
+
+int m3gpu_merge_batch_units_dev(
+    const int64_t* d_ts, const double* d_vals, const uint8_t* d_units,
+    const uint32_t* d_counts, uint32_t nreplicas, uint32_t nseries,
+    uint32_t stride, int64_t* d_out_ts, double* d_out_vals,
+    uint8_t* d_out_units, uint32_t* d_out_counts, int32_t* d_out_errs,
+    uint32_t out_stride, void* hip_stream) {
+    if (!nseries) return M3GPU_OK;
+    if (nreplicas < 1 || nreplicas > MERGE_MAX_R) {
+        snprintf(g_err, sizeof(g_err), "nreplicas must be 1..%d", MERGE_MAX_R);
+        return M3GPU_ERR_BADARG;
+    }
+    if (!d_units || !d_out_units) {
+        snprintf(g_err, sizeof(g_err), "d_units and d_out_units must be given");
+        return M3GPU_ERR_BADARG;
+    }
+    hipStream_t s = (hipStream_t)hip_stream;
+    hipLaunchKernelGGL(m3::k_merge<true>, dim3(grid_lane(nseries)),
+                       dim3(BLOCK_THREADS), 0, s,
+                       d_ts, d_vals, d_counts, nreplicas, nseries, stride,
+                       d_out_ts, d_out_vals, d_out_counts, d_out_errs,
+                       out_stride, d_units, d_out_units);
     HIP_TRY(hipGetLastError());
     return M3GPU_OK;
 }
@@ -3369,6 +3500,57 @@ int m3gpu_decode_batch_ann(
                        int_optimized, default_unit, out_ts, out_vals,
                        out_counts, out_errs, stride, true, out_ann,
                        ann_stride);
+}
+
+/* what a cgo ReaderIterator shim calls when Current()'s unit and the block
+ * start are wanted too; each optional output that is NULL is skipped */
+int m3gpu_decode_batch_full(
+    const uint8_t* blobs, uint64_t blobs_len,
+    const uint64_t* offsets, const uint32_t* lens,
+    uint32_t nseries, int int_optimized, uint8_t default_unit,
+    int64_t* out_ts, double* out_vals, uint32_t* out_counts,
+    int32_t* out_errs, uint32_t stride,
+    uint8_t* out_units, int64_t* out_start_ns,
+    uint8_t* out_ann, uint32_t ann_stride) {
+    if (!nseries) return M3GPU_OK;
+    int rc = decode_full_check_args(out_ann != nullptr, ann_stride);
+    if (rc != M3GPU_OK) return rc;
+    DevStreams in;
+    DevBuf<int64_t> d_ts, d_start;
+    DevBuf<double> d_vals;
+    DevBuf<uint32_t> d_counts;
+    DevBuf<int32_t> d_errs;
+    DevBuf<uint8_t> d_units, d_ann;
+    uint64_t npts = (uint64_t)nseries * stride;
+    uint64_t ann_total = (uint64_t)nseries * ann_stride;
+    HIP_TRY(in.upload(blobs, blobs_len, offsets, lens, nseries));
+    HIP_TRY(d_ts.alloc(npts));
+    HIP_TRY(d_vals.alloc(npts));
+    HIP_TRY(d_counts.alloc(nseries));
+    HIP_TRY(d_errs.alloc(nseries));
+    if (out_units) {
+        /* the kernel writes only decoded points: the rest comes back 0 */
+        HIP_TRY(d_units.alloc(npts));
+        HIP_TRY(hipMemset(d_units.p, 0, npts));
+    }
+    if (out_start_ns) HIP_TRY(d_start.alloc(nseries));
+    if (out_ann) {
+        HIP_TRY(d_ann.alloc(ann_total));
+        HIP_TRY(hipMemset(d_ann.p, 0, ann_total));
+    }
+    rc = m3gpu_decode_batch_full_dev(
+        in.blobs.p, in.offsets.p, in.lens.p, nullptr, nseries, int_optimized,
+        default_unit, d_ts.p, d_vals.p, d_counts.p, d_errs.p, stride,
+        d_units.p, d_start.p, d_ann.p, ann_stride, nullptr);
+    if (rc != M3GPU_OK) return rc;
+    HIP_TRY(d_ts.download(out_ts, npts));
+    HIP_TRY(d_vals.download(out_vals, npts));
+    HIP_TRY(d_counts.download(out_counts, nseries));
+    HIP_TRY(d_errs.download(out_errs, nseries));
+    if (out_units) HIP_TRY(d_units.download(out_units, npts));
+    if (out_start_ns) HIP_TRY(d_start.download(out_start_ns, nseries));
+    if (out_ann) HIP_TRY(d_ann.download(out_ann, ann_total));
+    return M3GPU_OK;
 }
 
 /* Both encode forms: upload the points (and, for the full form, whichever

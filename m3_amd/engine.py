@@ -69,6 +69,21 @@ def lib():
         L.m3gpu_decode_batch_dev_ann.argtypes = [c_vp, c_vp, c_vp, c_u32,
                                                  c_int, c_u8, c_vp, c_vp, c_vp,
                                                  c_vp, c_u32, c_vp, c_u32, c_vp]
+        L.m3gpu_decode_batch_full_dev.restype = c_int
+        L.m3gpu_decode_batch_full_dev.argtypes = [c_vp, c_vp, c_vp, c_vp, c_u32,
+                                                  c_int, c_u8, c_vp, c_vp, c_vp,
+                                                  c_vp, c_u32, c_vp, c_vp, c_vp,
+                                                  c_u32, c_vp]
+        L.m3gpu_decode_batch_full.restype = c_int
+        L.m3gpu_decode_batch_full.argtypes = [P(c_u8), c_u64, P(c_u64), P(c_u32),
+                                              c_u32, c_int, c_u8, P(c_i64),
+                                              P(c_f64), P(c_u32), P(c_i32),
+                                              c_u32, P(c_u8), P(c_i64), P(c_u8),
+                                              c_u32]
+        L.m3gpu_merge_batch_units_dev.restype = c_int
+        L.m3gpu_merge_batch_units_dev.argtypes = [c_vp, c_vp, c_vp, c_vp, c_u32,
+                                                  c_u32, c_u32, c_vp, c_vp, c_vp,
+                                                  c_vp, c_vp, c_u32, c_vp]
         L.m3gpu_decode_batch.restype = c_int
         L.m3gpu_decode_batch.argtypes = [P(c_u8), c_u64, P(c_u64), P(c_u32), c_u32,
                                          c_int, c_u8, P(c_i64), P(c_f64), P(c_u32),
@@ -165,6 +180,42 @@ def decode_batch(blob, offsets, lens, stride, int_optimized=True,
     if check_errors:
         _raise_series_errors(out_errs, "decode")
     return out_ts, out_vals, out_counts, out_errs
+
+
+def decode_batch_full(blob, offsets, lens, stride, int_optimized=True,
+                      default_unit=1, units=True, start_ns=True, ann_stride=0,
+                      check_errors=True):
+    """Host form of the full decode (ReaderIterator.Current()'s unit per
+    point, the block start and, with ann_stride > 0, the annotation regions).
+    Returns a dict: ts, vals, counts, errs, and units (uint8 [nseries,
+    stride], 0 past each count), start_ns (int64 [nseries]) and ann (uint8
+    [nseries, ann_stride]) for the outputs asked for, None for the others.
+    The arrays can go to encode_batch_full unchanged."""
+    blob = _np(blob, np.uint8)
+    offsets = _np(offsets, np.uint64)
+    lens = _np(lens, np.uint32)
+    nseries = len(lens)
+    out = dict(
+        ts=np.empty((nseries, stride), dtype=np.int64),
+        vals=np.empty((nseries, stride), dtype=np.float64),
+        counts=np.empty(nseries, dtype=np.uint32),
+        errs=np.empty(nseries, dtype=np.int32),
+        units=np.zeros((nseries, stride), dtype=np.uint8) if units else None,
+        start_ns=np.zeros(nseries, dtype=np.int64) if start_ns else None,
+        ann=(np.zeros((nseries, ann_stride), dtype=np.uint8)
+             if ann_stride else None))
+    rc = lib().m3gpu_decode_batch_full(
+        _pp(blob, c_u8), len(blob), _pp(offsets, c_u64), _pp(lens, c_u32),
+        nseries, 1 if int_optimized else 0, default_unit,
+        _pp(out["ts"], c_i64), _pp(out["vals"], c_f64),
+        _pp(out["counts"], c_u32), _pp(out["errs"], c_i32), stride,
+        _pp(out["units"], c_u8) if units else None,
+        _pp(out["start_ns"], c_i64) if start_ns else None,
+        _pp(out["ann"], c_u8) if ann_stride else None, ann_stride)
+    _check(rc, "m3gpu_decode_batch_full")
+    if check_errors:
+        _raise_series_errors(out["errs"], "decode")
+    return out
 
 
 def encode_batch(ts, vals, counts, int_optimized=True, unit=1,
@@ -301,6 +352,33 @@ def decode_batch_dev_ann(d_blob, d_offsets, d_lens, out_ts, out_vals,
         _dev_ptr(out_vals), _dev_ptr(out_counts), _dev_ptr(out_errs), stride,
         _dev_ptr(out_ann), out_ann.shape[1], _torch_stream())
     _check(rc, "m3gpu_decode_batch_dev_ann")
+
+
+def decode_batch_full_dev(d_blob, d_offsets, d_lens, out_ts, out_vals,
+                          out_counts, out_errs, out_units=None,
+                          out_start_ns=None, out_ann=None, int_optimized=True,
+                          default_unit=1, d_perm=None):
+    """Full decode: decode_batch_dev plus what ReaderIterator.Current()
+    returns beside the datapoint. Optional torch CUDA output tensors:
+    out_units uint8 [nseries, stride] (the unit of every decoded point; bytes
+    past a series' count are left alone; any storage offset works),
+    out_start_ns int64 [nseries] (the stream's first 64 bits, the block
+    start), out_ann uint8 [nseries, ann_stride] (regions as in
+    decode_batch_dev_ann). The outputs can be passed unchanged to
+    encode_batch_full_dev, which then reproduces the streams. With all three
+    None the outputs equal decode_batch_dev's."""
+    nseries = d_lens.numel()
+    stride = out_ts.shape[1]
+    rc = lib().m3gpu_decode_batch_full_dev(
+        _dev_ptr(d_blob), _dev_ptr(d_offsets), _dev_ptr(d_lens),
+        _dev_ptr(d_perm) if d_perm is not None else None, nseries,
+        1 if int_optimized else 0, default_unit, _dev_ptr(out_ts),
+        _dev_ptr(out_vals), _dev_ptr(out_counts), _dev_ptr(out_errs), stride,
+        _dev_ptr(out_units) if out_units is not None else None,
+        _dev_ptr(out_start_ns) if out_start_ns is not None else None,
+        _dev_ptr(out_ann) if out_ann is not None else None,
+        out_ann.shape[1] if out_ann is not None else 0, _torch_stream())
+    _check(rc, "m3gpu_decode_batch_full_dev")
 
 
 def parse_ann_region(region):
@@ -510,6 +588,24 @@ def merge_batch_dev(d_ts, d_vals, d_counts, nreplicas, out_ts, out_vals,
         nseries, stride, _dev_ptr(out_ts), _dev_ptr(out_vals),
         _dev_ptr(out_counts), _dev_ptr(out_errs), out_stride, _torch_stream())
     _check(rc, "m3gpu_merge_batch_dev")
+
+
+def merge_batch_units_dev(d_ts, d_vals, d_units, d_counts, nreplicas, out_ts,
+                          out_vals, out_units, out_counts, out_errs):
+    """merge_batch_dev that also carries each point's time unit
+    (MultiReaderIterator.Current()'s second return): d_units uint8
+    [nreplicas*nseries, stride] rows laid out like d_ts, out_units uint8
+    [nseries, out_stride]; an emitted point gets the unit of the replica
+    whose value it got."""
+    nseries = d_counts.numel() // nreplicas
+    stride = d_ts.shape[-1]
+    out_stride = out_ts.shape[-1]
+    rc = lib().m3gpu_merge_batch_units_dev(
+        _dev_ptr(d_ts), _dev_ptr(d_vals), _dev_ptr(d_units),
+        _dev_ptr(d_counts), nreplicas, nseries, stride, _dev_ptr(out_ts),
+        _dev_ptr(out_vals), _dev_ptr(out_units), _dev_ptr(out_counts),
+        _dev_ptr(out_errs), out_stride, _torch_stream())
+    _check(rc, "m3gpu_merge_batch_units_dev")
 
 
 # ========================= fileset volume reader =========================

@@ -11,7 +11,10 @@ Semantics mirrored:
   - Next() advances and reports whether a point is available
     (iterator.go:81-100: first Next positions on the first point);
   - Current() returns (timestamp_ns, value, unit) for the current point
-    and is only valid after a true Next() (types.go:200); CurrentAnnotation()
+    and is only valid after a true Next() (types.go:200). The unit is the
+    point's own when the iterator was built with the `units` rows of
+    m3gpu_decode_batch_full_dev, the constructor's `unit` otherwise;
+    CurrentAnnotation()
     gives the sticky annotation the reference returns as Current()'s third
     value (iterator.go:226-231) when the iterator was built with the
     annotation-set events of m3gpu_decode_batch_dev_ann;
@@ -27,12 +30,16 @@ from .engine import SERIES_ERRORS
 class SliceReaderIterator:
     """`encoding.ReaderIterator` over one decoded series row."""
 
-    def __init__(self, ts, vals, count, err=0, unit=1, ann_events=None):
+    def __init__(self, ts, vals, count, err=0, unit=1, ann_events=None,
+                 units=None):
         self._ts = ts
         self._vals = vals
         self._n = int(count)
         self._err = int(err)
         self._unit = unit
+        # optional per-point units (one row of decode_batch_full_dev's
+        # out_units): what Current() reports instead of `unit`
+        self._units = units
         self._i = -1
         # annotation-set events [(point_idx, bytes)] in stream order
         # (engine.parse_ann_region); carried forward like PrevAnt
@@ -55,7 +62,8 @@ class SliceReaderIterator:
     def Current(self):
         if self._i < 0 or self._i >= self._n:
             raise RuntimeError("Current() before a successful Next()")
-        return int(self._ts[self._i]), float(self._vals[self._i]), self._unit
+        unit = self._unit if self._units is None else int(self._units[self._i])
+        return int(self._ts[self._i]), float(self._vals[self._i]), unit
 
     def CurrentAnnotation(self):
         """The reference Current()'s third return (sticky PrevAnt,
@@ -70,7 +78,7 @@ class SliceReaderIterator:
         return SERIES_ERRORS.get(self._err, f"error {self._err}")
 
     def Close(self):
-        self._ts = self._vals = None
+        self._ts = self._vals = self._units = None
         self._n = 0
 
 
@@ -81,7 +89,8 @@ class BatchIterators:
     plus per-series counts/errs, e.g. the (moved-to-host) outputs of
     `decode_batch_dev` or `fileset_ingest_dev`."""
 
-    def __init__(self, ts, vals, counts, errs=None, unit=1, ann_regions=None):
+    def __init__(self, ts, vals, counts, errs=None, unit=1, ann_regions=None,
+                 units=None):
         self._ts = np.asarray(ts)
         self._vals = np.asarray(vals)
         self._counts = np.asarray(counts)
@@ -90,6 +99,9 @@ class BatchIterators:
         # optional [nseries, ann_stride] uint8 regions from
         # m3gpu_decode_batch_dev_ann
         self._ann = np.asarray(ann_regions) if ann_regions is not None else None
+        # optional [nseries, stride] uint8 per-point units from
+        # m3gpu_decode_batch_full_dev
+        self._units = np.asarray(units) if units is not None else None
 
     def __len__(self):
         return len(self._counts)
@@ -100,8 +112,10 @@ class BatchIterators:
         if self._ann is not None:
             from .engine import parse_ann_region
             events = parse_ann_region(self._ann[i])
+        units = self._units[i] if self._units is not None else None
         return SliceReaderIterator(self._ts[i], self._vals[i],
-                                   self._counts[i], err, self._unit, events)
+                                   self._counts[i], err, self._unit, events,
+                                   units)
 
     def __iter__(self):
         for i in range(len(self)):
