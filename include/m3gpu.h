@@ -310,6 +310,70 @@ int m3gpu_merge_batch_units_dev(
     uint8_t* d_out_units, uint32_t* d_out_counts, int32_t* d_out_errs,
     uint32_t out_stride, void* hip_stream);
 
+/* -------- batched SeriesIterator (replaces encoding.SeriesIterator,
+ * dbnode/encoding/series_iterator.go:74-215, as client/session.go builds it
+ * from fetched blocks): R <= 4 replicas of B blocks each merge into one row
+ * per series, with the query range and the tie rule applied. --------
+ *
+ * Inputs are the rows m3gpu_decode_batch*_dev writes for a batch of
+ * nreplicas*nblocks*nseries streams: block b of replica r of series i is row
+ * (r*nblocks + b)*nseries + i, with `stride` elements of d_ts and d_vals,
+ * `stride` bytes of d_units, and one entry of d_counts and d_errs. A series
+ * with fewer blocks has count-0 rows; a replica's blocks are consumed in
+ * order b = 0..nblocks-1. d_units NULL: units are not carried. d_errs NULL:
+ * every row decoded cleanly. Any alignment works; the kernel reads several
+ * points per load, about three times as fast, when d_ts and d_vals are
+ * 16-byte aligned, d_units 4-byte aligned and stride a multiple of 4.
+ *
+ * Per replica (MultiReaderIterator, one reader per block slice): inside a
+ * block an equal timestamp is skipped and a smaller one is
+ * M3GPU_SERIES_OUT_OF_ORDER; across a block boundary nothing is compared. A
+ * row with a nonzero d_errs entry yields its points, then its error.
+ * Across replicas (iterators.go): [start_ns, end_ns) filters only when both
+ * are nonzero (series_iterator.go:145); below start_ns a point is skipped, at
+ * the first point >= end_ns the replica is dropped. `strategy` is the
+ * reference's IterateEqualTimestampStrategy (iterators_types.go:37-56). An
+ * error while the replicas are first positioned leaves the series empty; a
+ * later one keeps the points emitted so far.
+ *
+ * Outputs: one row of out_stride elements per series; d_out_counts[i] points
+ * are written and nothing beyond them; d_out_errs[i] is 0,
+ * M3GPU_SERIES_OUT_OF_ORDER, M3GPU_SERIES_CAPACITY (the stored prefix stays)
+ * or a row's error. d_out_units (given exactly when d_units is) is a plain
+ * byte array, any base address, out_stride bytes per series; a point gets the
+ * unit of the replica whose value it got. Annotations and FirstAnnotation()
+ * are not carried.
+ *
+ * M3GPU_ERR_BADARG, before any HIP call: nreplicas 0 or > 4; nblocks, stride
+ * or out_stride 0; strategy outside 0..3; exactly one of d_units and
+ * d_out_units given. */
+enum { M3GPU_EQUAL_TS_LAST_PUSHED = 0, M3GPU_EQUAL_TS_HIGHEST_VALUE = 1,
+       M3GPU_EQUAL_TS_LOWEST_VALUE = 2, M3GPU_EQUAL_TS_HIGHEST_FREQUENCY = 3 };
+/* errOutOfOrderIterator, in d_out_errs of all three merge entries */
+enum { M3GPU_SERIES_OUT_OF_ORDER = 100 };
+
+int m3gpu_series_merge_batch_dev(
+    const int64_t* d_ts, const double* d_vals,
+    const uint8_t* d_units,      /* NULL => units not carried            */
+    const uint32_t* d_counts,
+    const int32_t* d_errs,       /* NULL => every row decoded cleanly    */
+    uint32_t nreplicas, uint32_t nblocks, uint32_t nseries, uint32_t stride,
+    int64_t start_ns, int64_t end_ns, int strategy,
+    int64_t* d_out_ts, double* d_out_vals,
+    uint8_t* d_out_units,        /* given iff d_units is                 */
+    uint32_t* d_out_counts, int32_t* d_out_errs, uint32_t out_stride,
+    void* hip_stream);
+
+/* host-pointer form: uploads, merges on the null stream, copies back; blocks.
+ * out_units bytes past a series' count come back 0. */
+int m3gpu_series_merge_batch(
+    const int64_t* ts, const double* vals, const uint8_t* units,
+    const uint32_t* counts, const int32_t* errs,
+    uint32_t nreplicas, uint32_t nblocks, uint32_t nseries, uint32_t stride,
+    int64_t start_ns, int64_t end_ns, int strategy,
+    int64_t* out_ts, double* out_vals, uint8_t* out_units,
+    uint32_t* out_counts, int32_t* out_errs, uint32_t out_stride);
+
 int m3gpu_rollup_batch(
     const uint8_t* blobs, uint64_t blobs_len,
     const uint64_t* offsets, const uint32_t* lens,

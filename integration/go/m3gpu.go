@@ -352,6 +352,47 @@ func MergeBatchUnits(
 	return nil
 }
 
+// The IterateEqualTimestampStrategy values SeriesMergeBatch takes
+// (M3GPU_EQUAL_TS_*; the order of encoding.IterateEqualTimestampStrategy).
+const (
+	EqualTsLastPushed       = 0
+	EqualTsHighestValue     = 1
+	EqualTsLowestValue      = 2
+	EqualTsHighestFrequency = 3
+)
+
+// SeriesMergeBatch is the batched encoding.SeriesIterator
+// (m3gpu_series_merge_batch_dev): nreplicas replicas of nblocks decoded
+// blocks per series merge into one row per series, with the query range
+// [startNs, endNs) (on only when both are nonzero) and the equal-timestamp
+// strategy applied. Like the C entry it works on DEVICE buffers: block b of
+// replica r of series i is row (r*nblocks+b)*nseries+i of dTs/dVals/dUnits
+// and entry of dCounts/dErrs — what DecodeBatch's device form writes for the
+// streams packed in that order. dUnits and dOutUnits go together (both nil:
+// units are not carried); dErrs may be nil. A per-series error leaves the
+// points emitted before it in place. Annotations are not carried. The work
+// is enqueued on hipStream (nil: the null stream); the caller synchronizes.
+func SeriesMergeBatch(
+	dTs, dVals, dUnits, dCounts, dErrs unsafe.Pointer,
+	nreplicas, nblocks, nseries, stride uint32,
+	startNs, endNs int64, strategy int,
+	dOutTs, dOutVals, dOutUnits, dOutCounts, dOutErrs unsafe.Pointer,
+	outStride uint32, hipStream unsafe.Pointer,
+) error {
+	rc := C.m3gpu_series_merge_batch_dev(
+		(*C.int64_t)(dTs), (*C.double)(dVals), (*C.uint8_t)(dUnits),
+		(*C.uint32_t)(dCounts), (*C.int32_t)(dErrs), C.uint32_t(nreplicas),
+		C.uint32_t(nblocks), C.uint32_t(nseries), C.uint32_t(stride),
+		C.int64_t(startNs), C.int64_t(endNs), C.int(strategy),
+		(*C.int64_t)(dOutTs), (*C.double)(dOutVals), (*C.uint8_t)(dOutUnits),
+		(*C.uint32_t)(dOutCounts), (*C.int32_t)(dOutErrs),
+		C.uint32_t(outStride), hipStream)
+	if rc != 0 {
+		return lastError()
+	}
+	return nil
+}
+
 // annRegionSize is the bytes one series' events need in an annotation
 // region: the event count, one 12-byte table entry per event, the bytes.
 func annRegionSize(evs []AnnotationEvent) uint64 {

@@ -15,6 +15,8 @@ this product path.
 """
 from .iterators import (  # noqa: F401
     BatchIterators,
+    BatchSeriesIterators,
+    SeriesIterator,
     SliceReaderIterator,
 )
 from .engine import (  # noqa: F401
@@ -38,8 +40,11 @@ from .engine import (  # noqa: F401
     encode_batch,
     encode_batch_dev,
     engine_available,
+    fetch_series_dev,
     lib,
     merge_batch_dev,
+    series_merge,
+    series_merge_dev,
     pack_streams,
     parse_unaggregated,
     regather_dev,

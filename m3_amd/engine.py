@@ -30,7 +30,11 @@ M3GPU_AGG = dict(last=1, min=2, max=3, mean=4, median=5, count=6, sum=7,
 
 SERIES_ERRORS = {0: "ok", 1: "eof", 2: "dod_overflow", 3: "no_scheme",
                  4: "invalid_mult", 5: "annotation", 6: "capacity",
-                 7: "unsorted", 8: "bucket_overflow"}
+                 7: "unsorted", 8: "bucket_overflow", 100: "out_of_order"}
+
+# IterateEqualTimestampStrategy (m3gpu.h M3GPU_EQUAL_TS_*)
+EQUAL_TS_LAST_PUSHED, EQUAL_TS_HIGHEST_VALUE = 0, 1
+EQUAL_TS_LOWEST_VALUE, EQUAL_TS_HIGHEST_FREQUENCY = 2, 3
 
 
 class M3GpuError(RuntimeError):
@@ -84,6 +88,19 @@ def lib():
         L.m3gpu_merge_batch_units_dev.argtypes = [c_vp, c_vp, c_vp, c_vp, c_u32,
                                                   c_u32, c_u32, c_vp, c_vp, c_vp,
                                                   c_vp, c_vp, c_u32, c_vp]
+        L.m3gpu_series_merge_batch_dev.restype = c_int
+        L.m3gpu_series_merge_batch_dev.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                   c_u32, c_u32, c_u32, c_u32,
+                                                   c_i64, c_i64, c_int, c_vp,
+                                                   c_vp, c_vp, c_vp, c_vp,
+                                                   c_u32, c_vp]
+        L.m3gpu_series_merge_batch.restype = c_int
+        L.m3gpu_series_merge_batch.argtypes = [P(c_i64), P(c_f64), P(c_u8),
+                                               P(c_u32), P(c_i32), c_u32,
+                                               c_u32, c_u32, c_u32, c_i64,
+                                               c_i64, c_int, P(c_i64),
+                                               P(c_f64), P(c_u8), P(c_u32),
+                                               P(c_i32), c_u32]
         L.m3gpu_decode_batch.restype = c_int
         L.m3gpu_decode_batch.argtypes = [P(c_u8), c_u64, P(c_u64), P(c_u32), c_u32,
                                          c_int, c_u8, P(c_i64), P(c_f64), P(c_u32),
@@ -606,6 +623,113 @@ def merge_batch_units_dev(d_ts, d_vals, d_units, d_counts, nreplicas, out_ts,
         _dev_ptr(out_vals), _dev_ptr(out_units), _dev_ptr(out_counts),
         _dev_ptr(out_errs), out_stride, _torch_stream())
     _check(rc, "m3gpu_merge_batch_units_dev")
+
+
+def series_merge_dev(d_ts, d_vals, d_counts, nreplicas, nblocks, out_ts,
+                     out_vals, out_counts, out_errs, d_units=None,
+                     out_units=None, d_errs=None, start_ns=0, end_ns=0,
+                     strategy=EQUAL_TS_LAST_PUSHED):
+    """Batched SeriesIterator (m3gpu_series_merge_batch_dev): nreplicas
+    replicas of nblocks decoded blocks per series merge into one row per
+    series. Rows of d_ts / d_vals / d_units ([rows, stride]) and entries of
+    d_counts / d_errs are ordered (r*nblocks + b)*nseries + i; outputs are
+    [nseries, out_stride]. [start_ns, end_ns) filters when both are nonzero;
+    strategy is one of EQUAL_TS_*. d_units and out_units go together."""
+    nseries = d_counts.numel() // (nreplicas * nblocks)
+    rc = lib().m3gpu_series_merge_batch_dev(
+        _dev_ptr(d_ts), _dev_ptr(d_vals),
+        _dev_ptr(d_units) if d_units is not None else None,
+        _dev_ptr(d_counts), _dev_ptr(d_errs) if d_errs is not None else None,
+        nreplicas, nblocks, nseries, d_ts.shape[-1], start_ns, end_ns,
+        strategy, _dev_ptr(out_ts), _dev_ptr(out_vals),
+        _dev_ptr(out_units) if out_units is not None else None,
+        _dev_ptr(out_counts), _dev_ptr(out_errs), out_ts.shape[-1],
+        _torch_stream())
+    _check(rc, "m3gpu_series_merge_batch_dev")
+
+
+def series_merge(ts, vals, counts, nreplicas, nblocks, out_stride, units=None,
+                 errs=None, start_ns=0, end_ns=0,
+                 strategy=EQUAL_TS_LAST_PUSHED):
+    """Host form of series_merge_dev over numpy arrays; blocks. Returns
+    (ts, vals, units or None, counts, errs)."""
+    ts = _np(ts, np.int64)
+    vals = _np(vals, np.float64)
+    counts = _np(counts, np.uint32)
+    stride = ts.shape[-1]
+    nseries = counts.size // (nreplicas * nblocks)
+    if units is not None:
+        units = _np(units, np.uint8)
+    if errs is not None:
+        errs = _np(errs, np.int32)
+    out_ts = np.zeros((nseries, out_stride), dtype=np.int64)
+    out_vals = np.zeros((nseries, out_stride), dtype=np.float64)
+    out_units = (np.zeros((nseries, out_stride), dtype=np.uint8)
+                 if units is not None else None)
+    out_counts = np.zeros(nseries, dtype=np.uint32)
+    out_errs = np.zeros(nseries, dtype=np.int32)
+    rc = lib().m3gpu_series_merge_batch(
+        _pp(ts, c_i64), _pp(vals, c_f64),
+        _pp(units, c_u8) if units is not None else None, _pp(counts, c_u32),
+        _pp(errs, c_i32) if errs is not None else None, nreplicas, nblocks,
+        nseries, stride, start_ns, end_ns, strategy, _pp(out_ts, c_i64),
+        _pp(out_vals, c_f64),
+        _pp(out_units, c_u8) if out_units is not None else None,
+        _pp(out_counts, c_u32), _pp(out_errs, c_i32), out_stride)
+    _check(rc, "m3gpu_series_merge_batch")
+    return out_ts, out_vals, out_units, out_counts, out_errs
+
+
+def fetch_series_dev(torch, d_blob, d_offsets, d_lens, nreplicas, nblocks,
+                     stride, start_ns=0, end_ns=0,
+                     strategy=EQUAL_TS_LAST_PUSHED, int_optimized=True,
+                     default_unit=1, with_units=False):
+    """What a query gets from a fetch of nblocks blocks x nreplicas replicas
+    per series (client/session.go builds an encoding.SeriesIterator from
+    them): decode every stream, then merge each series' replicas with the
+    range and the tie strategy applied. The nreplicas*nblocks*nseries streams
+    are packed in the order (r*nblocks + b)*nseries + i; `stride` is the
+    decode capacity per block. Decode errors travel into the merge, which
+    surfaces them the way the iterator would. Returns a dict of device
+    tensors: ts, vals ([nseries, out_stride], out_stride = nblocks*stride
+    rounded up to even), units (uint8, or None without with_units), counts,
+    errs. Enqueues on the current stream; the caller synchronizes."""
+    nrows = d_lens.numel()
+    nseries = nrows // (nreplicas * nblocks)
+    if nseries * nreplicas * nblocks != nrows:
+        raise M3GpuError(
+            f"{nrows} streams are not {nreplicas} replicas x {nblocks} blocks "
+            f"of a whole number of series")
+    dev = d_blob.device
+    r_ts = torch.empty((nrows, stride), dtype=torch.int64, device=dev)
+    r_vals = torch.empty((nrows, stride), dtype=torch.float64, device=dev)
+    r_counts = torch.empty(nrows, dtype=torch.int32, device=dev)
+    r_errs = torch.empty(nrows, dtype=torch.int32, device=dev)
+    r_units = None
+    if with_units:
+        r_units = torch.empty((nrows, stride), dtype=torch.uint8, device=dev)
+        decode_batch_full_dev(d_blob, d_offsets, d_lens, r_ts, r_vals,
+                              r_counts, r_errs, out_units=r_units,
+                              int_optimized=int_optimized,
+                              default_unit=default_unit)
+    else:
+        decode_batch_dev(d_blob, d_offsets, d_lens, r_ts, r_vals, r_counts,
+                         r_errs, int_optimized=int_optimized,
+                         default_unit=default_unit)
+    out_stride = (nblocks * stride + 1) & ~1
+    out = dict(
+        ts=torch.empty((nseries, out_stride), dtype=torch.int64, device=dev),
+        vals=torch.empty((nseries, out_stride), dtype=torch.float64,
+                         device=dev),
+        units=(torch.zeros((nseries, out_stride), dtype=torch.uint8,
+                           device=dev) if with_units else None),
+        counts=torch.empty(nseries, dtype=torch.int32, device=dev),
+        errs=torch.empty(nseries, dtype=torch.int32, device=dev))
+    series_merge_dev(r_ts, r_vals, r_counts, nreplicas, nblocks, out["ts"],
+                     out["vals"], out["counts"], out["errs"], d_units=r_units,
+                     out_units=out["units"], d_errs=r_errs, start_ns=start_ns,
+                     end_ns=end_ns, strategy=strategy)
+    return out
 
 
 # ========================= fileset volume reader =========================

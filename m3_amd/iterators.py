@@ -2,12 +2,20 @@
 
 The GPU engine returns decoded batches as SoA arrays; callers ported from
 the reference often want the `encoding.ReaderIterator` shape
-(dbnode/encoding/types.go:197-203: Next/Current/Err/Close) and the
-`SeriesIterator` multi-iteration. These wrappers mirror those semantics
-over decoded rows — host logic only, no compute (the GPU decode happened
-at the batch boundary; see INTEGRATION.md §3 for the Go-side equivalent).
+(dbnode/encoding/types.go:197-203: Next/Current/Err/Close) or, for a query,
+the `encoding.SeriesIterator` shape (types.go: Next/Current/Err/Start/End/
+Close). These wrappers give those shapes over rows the GPU already computed —
+host logic only, no compute, see INTEGRATION.md §3 for the Go-side equivalent:
 
-Semantics mirrored:
+  - SliceReaderIterator / BatchIterators walk DECODED rows (one stream
+    each); they merge nothing;
+  - SeriesIterator / BatchSeriesIterators walk MERGED rows, the output of
+    m3gpu_series_merge_batch_dev (engine.series_merge_dev /
+    fetch_series_dev): the replica merge, the block stitching, the range
+    filter and the equal-timestamp strategy all happened on the GPU, and the
+    wrapper only steps through the result.
+
+ReaderIterator semantics mirrored:
   - Next() advances and reports whether a point is available
     (iterator.go:81-100: first Next positions on the first point);
   - Current() returns (timestamp_ns, value, unit) for the current point
@@ -116,6 +124,90 @@ class BatchIterators:
         return SliceReaderIterator(self._ts[i], self._vals[i],
                                    self._counts[i], err, self._unit, events,
                                    units)
+
+    def __iter__(self):
+        for i in range(len(self)):
+            yield self.iterator(i)
+
+
+class SeriesIterator:
+    """`encoding.SeriesIterator` over one merged row of
+    m3gpu_series_merge_batch_dev. The series' error is sticky as in the
+    reference (series_iterator.go:74-91), but the points the merge emitted
+    before it stay readable: Next() turns false behind the last of them and
+    Err() then names the error. Annotations are not carried through the
+    merge, so there is no FirstAnnotation()."""
+
+    def __init__(self, ts, vals, count, err=0, start_ns=0, end_ns=0, unit=1,
+                 units=None):
+        self._ts = ts
+        self._vals = vals
+        self._units = units
+        self._n = int(count)
+        self._err = int(err)
+        self._start = int(start_ns)
+        self._end = int(end_ns)
+        self._unit = unit
+        self._i = -1
+        self._closed = False
+
+    def Next(self):
+        if self._closed or self._i + 1 >= self._n:
+            self._i = self._n
+            return False
+        self._i += 1
+        return True
+
+    def Current(self):
+        if self._i < 0 or self._i >= self._n:
+            raise RuntimeError("Current() before a successful Next()")
+        unit = self._unit if self._units is None else int(self._units[self._i])
+        return int(self._ts[self._i]), float(self._vals[self._i]), unit
+
+    def Err(self):
+        if self._err == 0:
+            return None
+        return SERIES_ERRORS.get(self._err, f"error {self._err}")
+
+    def Start(self):
+        """StartInclusive of the query range (0: unfiltered)."""
+        return self._start
+
+    def End(self):
+        """EndExclusive of the query range (0: unfiltered)."""
+        return self._end
+
+    def Close(self):
+        self._closed = True
+        self._ts = self._vals = self._units = None
+        self._n = 0
+
+
+class BatchSeriesIterators:
+    """Per-series SeriesIterators over a merged batch: numpy arrays or torch
+    CPU tensors [nseries, out_stride] plus counts/errs, e.g. the
+    (moved-to-host) outputs of engine.series_merge_dev or fetch_series_dev,
+    with the range the merge was given."""
+
+    def __init__(self, ts, vals, counts, errs=None, start_ns=0, end_ns=0,
+                 unit=1, units=None):
+        self._ts = np.asarray(ts)
+        self._vals = np.asarray(vals)
+        self._counts = np.asarray(counts)
+        self._errs = np.asarray(errs) if errs is not None else None
+        self._units = np.asarray(units) if units is not None else None
+        self._start = start_ns
+        self._end = end_ns
+        self._unit = unit
+
+    def __len__(self):
+        return len(self._counts)
+
+    def iterator(self, i):
+        err = int(self._errs[i]) if self._errs is not None else 0
+        units = self._units[i] if self._units is not None else None
+        return SeriesIterator(self._ts[i], self._vals[i], self._counts[i],
+                              err, self._start, self._end, self._unit, units)
 
     def __iter__(self):
         for i in range(len(self)):
