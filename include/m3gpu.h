@@ -374,6 +374,84 @@ int m3gpu_series_merge_batch(
     int64_t* out_ts, double* out_vals, uint8_t* out_units,
     uint32_t* out_counts, int32_t* out_errs, uint32_t out_stride);
 
+/* -------- batched StepIter (replaces encodedBlock.StepIter(),
+ * query/storage/m3/encoded_step_iterator.go; nextForStep,
+ * encoded_step_iterator_generic.go:63-119; StepLookbackConsolidator,
+ * consolidators/step_consolidator.go, with TakeLast,
+ * consolidators/types.go:207-216): every series is consolidated onto the
+ * query's step grid, one float64 per (step, series). --------
+ *
+ * Grid: t_k = start_ns + k*step_ns, k = 0..nsteps-1. value(k) is the value,
+ * bit for bit, of the last point with t_k - lookback_ns <= ts <= t_k (both
+ * ends inclusive) whose value is not NaN; with none, the bit pattern
+ * 0x7FF8000000000001 (Go's math.NaN()). Output is step-major, the
+ * reference's block.ColStep columns: d_out[k*out_pitch + i], out_pitch >=
+ * nseries. Exactly nsteps*nseries cells and d_out_errs[nseries] are written.
+ *
+ * Points are read up to and including the first with ts > t_last (the
+ * peeked point of nextForStep) and nothing after it. An error counts only
+ * if reading reaches it, i.e. no point read lies past t_last: a stream's
+ * decode error, a row's d_errs entry (it comes after the row's points), or
+ * M3GPU_SERIES_OUT_OF_ORDER. A series with a nonzero d_out_errs entry has
+ * its whole column set to the NaN pattern; the other series are kept (the
+ * reference fails the whole block). Only TakeLast is built.
+ *
+ * m3gpu_step_consolidate_batch_dev takes rows as m3gpu_series_merge_batch_dev
+ * or a decode writes them: d_ts, d_vals [nseries, stride], d_counts, and
+ * d_errs (NULL: every row is clean). A point with ts <= its predecessor is
+ * M3GPU_SERIES_OUT_OF_ORDER: the reference's arrival-order buffer gives an
+ * unspecified result there, and a SeriesIterator never yields it for
+ * time-ordered blocks. Any alignment works; 16-byte aligned arrays and an
+ * even stride read two points a load.
+ *
+ * m3gpu_decode_steps_batch_dev goes from streams to the matrix with no rows
+ * in between, for one replica: series i has nblocks streams at index
+ * b*nseries + i (layout contract of m3gpu_decode_batch above), read in order
+ * b = 0..nblocks-1; a zero-length stream is an absent block. An equal
+ * timestamp is skipped and a smaller one is M3GPU_SERIES_OUT_OF_ORDER, inside
+ * a stream and across a boundary, which is what the one-replica
+ * m3gpu_series_merge_batch_dev yields: the result equals
+ * m3gpu_step_consolidate_batch_dev over that merge (no range) over the
+ * decode of the streams with the errors of zero-length streams cleared. It
+ * stops decoding a series at the first point past t_last.
+ *
+ * M3GPU_ERR_BADARG, before any HIP call: step_ns <= 0; lookback_ns < 0;
+ * nsteps 0; stride or nblocks 0; out_pitch < nseries; start_ns +
+ * (nsteps-1)*step_ns or start_ns - lookback_ns outside int64. nseries 0
+ * succeeds and does nothing. */
+int m3gpu_step_consolidate_batch_dev(
+    const int64_t* d_ts, const double* d_vals, const uint32_t* d_counts,
+    const int32_t* d_errs,       /* NULL => every row is clean           */
+    uint32_t nseries, uint32_t stride,
+    int64_t start_ns, int64_t step_ns, uint32_t nsteps, int64_t lookback_ns,
+    double* d_out, uint32_t out_pitch, int32_t* d_out_errs,
+    void* hip_stream);
+
+int m3gpu_decode_steps_batch_dev(
+    const uint8_t* d_blobs, const uint64_t* d_offsets, const uint32_t* d_lens,
+    uint32_t nseries, uint32_t nblocks, int int_optimized,
+    uint8_t default_unit,
+    int64_t start_ns, int64_t step_ns, uint32_t nsteps, int64_t lookback_ns,
+    double* d_out, uint32_t out_pitch, int32_t* d_out_errs,
+    void* hip_stream);
+
+/* host-pointer forms: upload, run on the null stream, copy back; block.
+ * out is [nsteps, out_pitch]; cells past nseries in a row are left alone.
+ * offsets and lens have nseries*nblocks entries. */
+int m3gpu_step_consolidate_batch(
+    const int64_t* ts, const double* vals, const uint32_t* counts,
+    const int32_t* errs, uint32_t nseries, uint32_t stride,
+    int64_t start_ns, int64_t step_ns, uint32_t nsteps, int64_t lookback_ns,
+    double* out, uint32_t out_pitch, int32_t* out_errs);
+
+int m3gpu_decode_steps_batch(
+    const uint8_t* blobs, uint64_t blobs_len,
+    const uint64_t* offsets, const uint32_t* lens,
+    uint32_t nseries, uint32_t nblocks, int int_optimized,
+    uint8_t default_unit,
+    int64_t start_ns, int64_t step_ns, uint32_t nsteps, int64_t lookback_ns,
+    double* out, uint32_t out_pitch, int32_t* out_errs);
+
 int m3gpu_rollup_batch(
     const uint8_t* blobs, uint64_t blobs_len,
     const uint64_t* offsets, const uint32_t* lens,

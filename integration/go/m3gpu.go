@@ -393,6 +393,71 @@ func SeriesMergeBatch(
 	return nil
 }
 
+// StepNaNBits is what a step without a value holds: Go's math.NaN().
+const StepNaNBits = 0x7FF8000000000001
+
+// StepConsolidateBatch is the batched encodedBlock.StepIter() over rows
+// (m3gpu_step_consolidate_batch_dev; query/storage/m3/
+// encoded_step_iterator_generic.go:63-119 nextForStep,
+// consolidators/step_consolidator.go, consolidators/types.go:207-216
+// TakeLast): the rows SeriesMergeBatch or DecodeBatch's device form wrote
+// (dTs, dVals [nseries, stride], dCounts, dErrs or nil) are consolidated onto
+// the grid startNs + k*stepNs, k < nsteps, with the last non-NaN value in
+// [t_k - lookbackNs, t_k]. dOut is step-major, the block.ColStep layout:
+// dOut[k*outPitch + i], a step without a value holding StepNaNBits.
+// dOutErrs[i] != 0 (a row's error that reading reached, or 100 for a
+// timestamp at or before its predecessor) means series i's column is all
+// NaN; the reference fails the whole block there. DEVICE buffers, enqueued on
+// hipStream (nil: the null stream); the caller synchronizes.
+func StepConsolidateBatch(
+	dTs, dVals, dCounts, dErrs unsafe.Pointer,
+	nseries, stride uint32,
+	startNs, stepNs int64, nsteps uint32, lookbackNs int64,
+	dOut unsafe.Pointer, outPitch uint32, dOutErrs unsafe.Pointer,
+	hipStream unsafe.Pointer,
+) error {
+	rc := C.m3gpu_step_consolidate_batch_dev(
+		(*C.int64_t)(dTs), (*C.double)(dVals), (*C.uint32_t)(dCounts),
+		(*C.int32_t)(dErrs), C.uint32_t(nseries), C.uint32_t(stride),
+		C.int64_t(startNs), C.int64_t(stepNs), C.uint32_t(nsteps),
+		C.int64_t(lookbackNs), (*C.double)(dOut), C.uint32_t(outPitch),
+		(*C.int32_t)(dOutErrs), hipStream)
+	if rc != 0 {
+		return lastError()
+	}
+	return nil
+}
+
+// DecodeStepsBatch goes from streams to the step matrix in one kernel, for
+// one replica (m3gpu_decode_steps_batch_dev): series i has nblocks streams
+// at index b*nseries+i of dOffsets/dLens, read in block order, a zero-length
+// stream being an absent block. No rows are written, and a series stops
+// decoding at its first point past the last step. Outputs as in
+// StepConsolidateBatch; with more than one replica use DecodeBatch,
+// SeriesMergeBatch and StepConsolidateBatch.
+func DecodeStepsBatch(
+	dBlobs, dOffsets, dLens unsafe.Pointer,
+	nseries, nblocks uint32, intOptimized bool, defaultUnit byte,
+	startNs, stepNs int64, nsteps uint32, lookbackNs int64,
+	dOut unsafe.Pointer, outPitch uint32, dOutErrs unsafe.Pointer,
+	hipStream unsafe.Pointer,
+) error {
+	intOpt := C.int(0)
+	if intOptimized {
+		intOpt = 1
+	}
+	rc := C.m3gpu_decode_steps_batch_dev(
+		(*C.uint8_t)(dBlobs), (*C.uint64_t)(dOffsets), (*C.uint32_t)(dLens),
+		C.uint32_t(nseries), C.uint32_t(nblocks), intOpt,
+		C.uint8_t(defaultUnit), C.int64_t(startNs), C.int64_t(stepNs),
+		C.uint32_t(nsteps), C.int64_t(lookbackNs), (*C.double)(dOut),
+		C.uint32_t(outPitch), (*C.int32_t)(dOutErrs), hipStream)
+	if rc != 0 {
+		return lastError()
+	}
+	return nil
+}
+
 // annRegionSize is the bytes one series' events need in an annotation
 // region: the event count, one 12-byte table entry per event, the bytes.
 func annRegionSize(evs []AnnotationEvent) uint64 {

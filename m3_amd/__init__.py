@@ -18,6 +18,7 @@ from .iterators import (  # noqa: F401
     BatchSeriesIterators,
     SeriesIterator,
     SliceReaderIterator,
+    StepIter,
 )
 from .engine import (  # noqa: F401
     CL_ERRORS,
@@ -40,11 +41,15 @@ from .engine import (  # noqa: F401
     encode_batch,
     encode_batch_dev,
     engine_available,
+    decode_steps_dev,
     fetch_series_dev,
+    fetch_steps_dev,
     lib,
     merge_batch_dev,
     series_merge,
     series_merge_dev,
+    step_consolidate,
+    step_consolidate_dev,
     pack_streams,
     parse_unaggregated,
     regather_dev,

@@ -101,6 +101,28 @@ def lib():
                                                c_i64, c_int, P(c_i64),
                                                P(c_f64), P(c_u8), P(c_u32),
                                                P(c_i32), c_u32]
+        L.m3gpu_step_consolidate_batch_dev.restype = c_int
+        L.m3gpu_step_consolidate_batch_dev.argtypes = [c_vp, c_vp, c_vp, c_vp,
+                                                       c_u32, c_u32, c_i64,
+                                                       c_i64, c_u32, c_i64,
+                                                       c_vp, c_u32, c_vp, c_vp]
+        L.m3gpu_decode_steps_batch_dev.restype = c_int
+        L.m3gpu_decode_steps_batch_dev.argtypes = [c_vp, c_vp, c_vp, c_u32,
+                                                   c_u32, c_int, c_u8, c_i64,
+                                                   c_i64, c_u32, c_i64, c_vp,
+                                                   c_u32, c_vp, c_vp]
+        L.m3gpu_step_consolidate_batch.restype = c_int
+        L.m3gpu_step_consolidate_batch.argtypes = [P(c_i64), P(c_f64),
+                                                   P(c_u32), P(c_i32), c_u32,
+                                                   c_u32, c_i64, c_i64, c_u32,
+                                                   c_i64, P(c_f64), c_u32,
+                                                   P(c_i32)]
+        L.m3gpu_decode_steps_batch.restype = c_int
+        L.m3gpu_decode_steps_batch.argtypes = [P(c_u8), c_u64, P(c_u64),
+                                               P(c_u32), c_u32, c_u32, c_int,
+                                               c_u8, c_i64, c_i64, c_u32,
+                                               c_i64, P(c_f64), c_u32,
+                                               P(c_i32)]
         L.m3gpu_decode_batch.restype = c_int
         L.m3gpu_decode_batch.argtypes = [P(c_u8), c_u64, P(c_u64), P(c_u32), c_u32,
                                          c_int, c_u8, P(c_i64), P(c_f64), P(c_u32),
@@ -729,6 +751,127 @@ def fetch_series_dev(torch, d_blob, d_offsets, d_lens, nreplicas, nblocks,
                      out["vals"], out["counts"], out["errs"], d_units=r_units,
                      out_units=out["units"], d_errs=r_errs, start_ns=start_ns,
                      end_ns=end_ns, strategy=strategy)
+    return out
+
+
+# Go's math.NaN(): what a step without a value holds
+STEP_NAN_BITS = 0x7FF8000000000001
+
+
+def step_consolidate_dev(d_ts, d_vals, d_counts, start_ns, step_ns, nsteps,
+                         lookback_ns, out, out_errs, d_errs=None):
+    """Batched StepIter over rows (m3gpu_step_consolidate_batch_dev): d_ts /
+    d_vals [nseries, stride] with d_counts and optional d_errs, as
+    series_merge_dev or a decode writes them, consolidate onto the grid
+    start_ns + k*step_ns with TakeLast over [t_k - lookback_ns, t_k]. out is
+    float64 [nsteps, out_pitch >= nseries], step-major; out_errs int32
+    [nseries]; a failed series' column is all NaN. Enqueues on the current
+    stream."""
+    nseries = d_counts.numel()
+    rc = lib().m3gpu_step_consolidate_batch_dev(
+        _dev_ptr(d_ts), _dev_ptr(d_vals), _dev_ptr(d_counts),
+        _dev_ptr(d_errs) if d_errs is not None else None, nseries,
+        d_ts.shape[-1], start_ns, step_ns, nsteps, lookback_ns, _dev_ptr(out),
+        out.stride(0) if out.dim() == 2 else nseries, _dev_ptr(out_errs),
+        _torch_stream())
+    _check(rc, "m3gpu_step_consolidate_batch_dev")
+
+
+def step_consolidate(ts, vals, counts, start_ns, step_ns, nsteps, lookback_ns,
+                     errs=None):
+    """Host form of step_consolidate_dev over numpy arrays; blocks. Returns
+    (steps float64 [nsteps, nseries], errs int32 [nseries])."""
+    ts = _np(ts, np.int64)
+    vals = _np(vals, np.float64)
+    counts = _np(counts, np.uint32)
+    if errs is not None:
+        errs = _np(errs, np.int32)
+    nseries = counts.size
+    stride = ts.shape[-1] if ts.ndim == 2 else 0
+    out = np.zeros((nsteps, nseries), dtype=np.float64)
+    out_errs = np.zeros(nseries, dtype=np.int32)
+    rc = lib().m3gpu_step_consolidate_batch(
+        _pp(ts, c_i64), _pp(vals, c_f64), _pp(counts, c_u32),
+        _pp(errs, c_i32) if errs is not None else None, nseries, stride,
+        start_ns, step_ns, nsteps, lookback_ns, _pp(out, c_f64), nseries,
+        _pp(out_errs, c_i32))
+    _check(rc, "m3gpu_step_consolidate_batch")
+    return out, out_errs
+
+
+def decode_steps_dev(d_blob, d_offsets, d_lens, nblocks, start_ns, step_ns,
+                     nsteps, lookback_ns, out, out_errs, int_optimized=True,
+                     default_unit=1):
+    """Fused decode -> StepIter for one replica
+    (m3gpu_decode_steps_batch_dev): the nblocks*nseries streams are packed in
+    the order b*nseries + i, a zero-length stream being an absent block; out
+    and out_errs as in step_consolidate_dev. No rows are written, and a
+    series stops decoding at its first point past the last step."""
+    nrows = d_lens.numel()
+    nseries = nrows // nblocks if nblocks else 0
+    if nblocks and nseries * nblocks != nrows:
+        raise M3GpuError(
+            f"{nrows} streams are not {nblocks} blocks of a whole number of "
+            f"series")
+    rc = lib().m3gpu_decode_steps_batch_dev(
+        _dev_ptr(d_blob), _dev_ptr(d_offsets), _dev_ptr(d_lens), nseries,
+        nblocks, 1 if int_optimized else 0, default_unit, start_ns, step_ns,
+        nsteps, lookback_ns, _dev_ptr(out),
+        out.stride(0) if out.dim() == 2 else nseries, _dev_ptr(out_errs),
+        _torch_stream())
+    _check(rc, "m3gpu_decode_steps_batch_dev")
+
+
+def fetch_steps_dev(torch, d_blob, d_offsets, d_lens, nreplicas, nblocks,
+                    stride, start_ns, step_ns, nsteps, lookback_ns,
+                    strategy=EQUAL_TS_LAST_PUSHED, int_optimized=True,
+                    default_unit=1):
+    """What encodedBlock.StepIter() walks for a fetch of nblocks blocks x
+    nreplicas replicas per series: the step x series matrix. One replica
+    takes the fused kernel (decode_steps_dev; `stride` is not used);
+    otherwise decode, series merge (no range filter: the consolidation reads
+    nothing past the last step and drops what lies before the first window)
+    and step_consolidate_dev, with a zero-length stream an absent block on
+    both paths. Streams are packed as for fetch_series_dev. Returns a dict of
+    device tensors: steps float64 [nsteps, nseries] (steps.T is the
+    per-series view) and errs int32 [nseries]. Enqueues on the current
+    stream; the caller synchronizes."""
+    nrows = d_lens.numel()
+    nseries = nrows // (nreplicas * nblocks)
+    if nseries * nreplicas * nblocks != nrows:
+        raise M3GpuError(
+            f"{nrows} streams are not {nreplicas} replicas x {nblocks} blocks "
+            f"of a whole number of series")
+    dev = d_blob.device
+    out = dict(
+        steps=torch.empty((nsteps, nseries), dtype=torch.float64, device=dev),
+        errs=torch.empty(nseries, dtype=torch.int32, device=dev))
+    if nreplicas == 1:
+        decode_steps_dev(d_blob, d_offsets, d_lens, nblocks, start_ns,
+                         step_ns, nsteps, lookback_ns, out["steps"],
+                         out["errs"], int_optimized=int_optimized,
+                         default_unit=default_unit)
+        return out
+    r_ts = torch.empty((nrows, stride), dtype=torch.int64, device=dev)
+    r_vals = torch.empty((nrows, stride), dtype=torch.float64, device=dev)
+    r_counts = torch.empty(nrows, dtype=torch.int32, device=dev)
+    r_errs = torch.empty(nrows, dtype=torch.int32, device=dev)
+    decode_batch_dev(d_blob, d_offsets, d_lens, r_ts, r_vals, r_counts,
+                     r_errs, int_optimized=int_optimized,
+                     default_unit=default_unit)
+    # an absent block is no reader at all, not one that fails with EOF
+    r_errs.masked_fill_(d_lens == 0, 0)
+    out_stride = (nblocks * stride + 1) & ~1
+    m_ts = torch.empty((nseries, out_stride), dtype=torch.int64, device=dev)
+    m_vals = torch.empty((nseries, out_stride), dtype=torch.float64,
+                         device=dev)
+    m_counts = torch.empty(nseries, dtype=torch.int32, device=dev)
+    m_errs = torch.empty(nseries, dtype=torch.int32, device=dev)
+    series_merge_dev(r_ts, r_vals, r_counts, nreplicas, nblocks, m_ts, m_vals,
+                     m_counts, m_errs, d_errs=r_errs, strategy=strategy)
+    step_consolidate_dev(m_ts, m_vals, m_counts, start_ns, step_ns, nsteps,
+                         lookback_ns, out["steps"], out["errs"],
+                         d_errs=m_errs)
     return out
 
 

@@ -13,7 +13,10 @@ host logic only, no compute, see INTEGRATION.md §3 for the Go-side equivalent:
     m3gpu_series_merge_batch_dev (engine.series_merge_dev /
     fetch_series_dev): the replica merge, the block stitching, the range
     filter and the equal-timestamp strategy all happened on the GPU, and the
-    wrapper only steps through the result.
+    wrapper only steps through the result;
+  - StepIter walks the step x series matrix of
+    m3gpu_step_consolidate_batch_dev / m3gpu_decode_steps_batch_dev in the
+    `block.StepIter` shape.
 
 ReaderIterator semantics mirrored:
   - Next() advances and reports whether a point is available
@@ -212,3 +215,51 @@ class BatchSeriesIterators:
     def __iter__(self):
         for i in range(len(self)):
             yield self.iterator(i)
+
+
+class StepIter:
+    """`block.StepIter` (query/block/types.go: Next/Current/StepCount/Err)
+    over the step x series matrix of m3gpu_step_consolidate_batch_dev or
+    m3gpu_decode_steps_batch_dev (engine.step_consolidate_dev,
+    decode_steps_dev, fetch_steps_dev), moved to the host: the consolidation
+    happened on the GPU and the wrapper only steps through the rows.
+    Current() returns (step time in ns, the step's column: one float64 per
+    series, a view). As in the reference (encoded_step_iterator_generic.go:
+    156-158,191-194) one series' error fails the block: Next() is false from
+    the start and Err() names the first failed series. The matrix keeps the
+    other series' columns; series_errors=False walks them, the failed
+    series' columns being all NaN."""
+
+    def __init__(self, steps, errs, start_ns, step_ns, series_errors=True):
+        self._steps = np.asarray(steps)
+        self._start = int(start_ns)
+        self._step = int(step_ns)
+        self._k = -1
+        self._err = None
+        errs = np.asarray(errs)
+        bad = np.nonzero(errs)[0]
+        if series_errors and len(bad):
+            code = int(errs[bad[0]])
+            self._err = (f"series {int(bad[0])}: "
+                         f"{SERIES_ERRORS.get(code, f'error {code}')}")
+
+    def StepCount(self):
+        return self._steps.shape[0]
+
+    def Next(self):
+        if self._err is not None or self._k + 1 >= self.StepCount():
+            self._k = self.StepCount()
+            return False
+        self._k += 1
+        return True
+
+    def Current(self):
+        if self._k < 0 or self._k >= self.StepCount():
+            raise RuntimeError("Current() before a successful Next()")
+        return self._start + self._k * self._step, self._steps[self._k]
+
+    def Err(self):
+        return self._err
+
+    def Close(self):
+        self._steps = self._steps[:0]
