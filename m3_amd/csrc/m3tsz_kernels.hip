@@ -17,11 +17,14 @@
  *        (8 of 8B when the outputs are not 16-byte aligned), which keeps
  *        write traffic at the algorithmic 16 B/pt.
  *      encode: each lane emits completed 64-bit words into its own row.
- *      rollup: the lane tier keeps per-bucket state in registers and small
- *        quantile buckets in a per-lane sorted LDS row; deep buckets retry
- *        on the wave-per-series tiers (k_rollup_batch, k_rollup_ckms),
- *        which run ONE series per wavefront with a wave-uniform parser and
- *        reproduce the reference CKMS walk exactly.
+ *      rollup (rollup_kernels.h, included below the decoders): the lane
+ *        tier keeps per-bucket state in registers and small quantile
+ *        buckets in a per-lane sorted LDS row; deep buckets retry on the
+ *        wave-per-series tiers (k_rollup_batch, k_rollup_ckms), which run
+ *        ONE series per wavefront with a wave-uniform parser and reproduce
+ *        the reference CKMS walk exactly. All three tiers share one bucket
+ *        walk, accumulate and ValueOf (rollup_bucket.h) and one
+ *        exact-quantile index (rollup_plan.h), both host-compilable.
  *  - Streams are decoded from 8-byte-aligned offsets, zero-padded to an
  *    8-byte boundary (layout contract in m3gpu.h; pack_streams emits 64B
  *    alignment, which satisfies it) so every refill is an aligned u64 load.
@@ -37,6 +40,7 @@
 #include <stdio.h>
 #include "../../include/m3gpu.h"
 #include "rollup_plan.h" /* QCAP, MAX_AGGS, m3::RollupPlan + its host builder */
+#include "rollup_bucket.h" /* go_f2i; the rollup tiers' shared bucket code */
 
 /* ========================= shared constants ========================= */
 /* m3tsz.go:28-62, scheme.go:28-52, x/time/unit.go:30-42 */
@@ -92,11 +96,8 @@ __device__ __forceinline__ double exp10_sel(uint8_t m) {
     return r;
 }
 
-/* Go float64->int64 (amd64 CVTTSD2SQ): out-of-range/NaN -> INT64_MIN */
-__device__ __forceinline__ int64_t go_f2i(double v) {
-    if (!(v >= -9223372036854775808.0 && v < 9223372036854775808.0)) return INT64_MIN;
-    return (int64_t)v;
-}
+/* go_f2i (Go's float64->int64) is in rollup_bucket.h: the counter rollup and
+ * its host-side test need it too */
 __device__ __forceinline__ uint64_t f2bits(double v) { return __double_as_longlong(v); }
 __device__ __forceinline__ double bits2f(uint64_t b) { return __longlong_as_double((long long)b); }
 
@@ -1907,232 +1908,6 @@ k_encode_batch(const int64_t* __restrict__ ts, const double* __restrict__ vals,
     }
 }
 
-/* ===================== fused decode -> rollup kernel ===================== */
-/* Reference semantics:
- *  bucket assignment  generic_elem.go:219-221 (truncate to window)
- *  output timestamp   list.go:541-543 (window END)
- *  Counter            counter.go:52-131  (int64 sum/min/max/count/sumSq)
- *  Gauge              gauge.go:73-165    (NaN rules :87-98; last by ts order)
- *  Timer              timer.go:56-153 over the CKMS stream; for <= 64 values
- *                     per bucket the production-default CKMS (eps=1e-3,
- *                     insertAndCompressEvery=1024) equals the no-compression
- *                     calcQuantiles walk (stream.go:231-277), implemented
- *                     here exactly (incl. the one-emission-per-sample shift
- *                     for colliding ranks); >64 values flags
- *                     M3GPU_SERIES_BUCKET_OVERFLOW.
- */
-
-struct BucketState {
-    int64_t isum, imin, imax, isumsq;
-    double fsum, fsumsq, fmin, fmax, last;
-    int64_t last_at;
-    int64_t count;
-
-    __device__ __forceinline__ void reset() {
-        isum = 0; isumsq = 0;
-        imin = INT64_MAX; imax = INT64_MIN;   /* counter.go:44-47 */
-        fsum = 0; fsumsq = 0;
-        fmin = __longlong_as_double(0x7ff8000000000000LL); /* NaN, gauge.go:56-59 */
-        fmax = __longlong_as_double(0x7ff8000000000000LL);
-        last = 0; last_at = 0;
-        count = 0;
-    }
-};
-
-__device__ __forceinline__ double m3_stdev(int64_t count, double sum_sq, double sum) { /* common.go:29-36 */
-    int64_t div = count * (count - 1);
-    if (div == 0) return 0.0;
-    return sqrt(((double)count * sum_sq - sum * sum) / (double)div);
-}
-
-__global__ void __launch_bounds__(BLOCK_THREADS)
-k_rollup_batch(const uint8_t* __restrict__ blobs,
-               const uint64_t* __restrict__ offsets,
-               const uint32_t* __restrict__ lens,
-               const int32_t* __restrict__ select, /* optional series subset */
-               uint32_t nseries, int int_optimized, uint8_t default_unit,
-               int metric_type, int64_t window_ns, uint32_t nbuckets,
-               RollupPlan plan,
-               double* __restrict__ out, int64_t* __restrict__ out_window_ts,
-               int32_t* __restrict__ out_errs) {
-    /* readfirstlane makes the series index provably wave-uniform: the
-     * whole parser then compiles to scalar (SGPR) code with scalar
-     * branches instead of exec-mask divergence sequences. */
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
-    const uint32_t lane = threadIdx.x % WAVE;
-    const uint32_t slot = blockIdx.x * WAVES_PER_BLOCK + wave;
-    const uint32_t series = __builtin_amdgcn_readfirstlane(
-        (select && slot < nseries) ? (uint32_t)select[slot] : slot);
-    /* per-wave bucket value staging for quantiles (timer) */
-    __shared__ double qvals_all[WAVES_PER_BLOCK][QCAP];
-    __shared__ double sorted_all[WAVES_PER_BLOCK][QCAP];
-    double* qvals = qvals_all[wave];
-    double* sorted = sorted_all[wave];
-    if (slot >= nseries) return;
-
-    Decoder d;
-    d.init(blobs, offsets[series], lens[series], int_optimized != 0, default_unit);
-
-    double* out_row = out + (uint64_t)series * nbuckets * plan.naggs;
-    int64_t* wts_row = out_window_ts ? out_window_ts + (uint64_t)series * nbuckets : nullptr;
-
-    BucketState bs;
-    bs.reset();
-    int64_t base = 0;
-    int64_t cur_bucket = -1;
-    uint32_t nq_in_bucket = 0;
-    int err = 0;
-
-    auto emit_bucket = [&](int64_t b) {
-        if (b < 0 || b >= (int64_t)nbuckets) return;
-        if (wts_row && lane == 0) wts_row[b] = base + (b + 1) * window_ns;
-        uint32_t n = nq_in_bucket;
-        /* quantile targets: the no-compression calcQuantiles walk closed
-         * form: k_i = max(rank_i, k_{i-1}+1), value = sorted[min(k_i,n)-1];
-         * n<=3: sorted[min(int(q*n), n-1)] (quantilesFromBuf) */
-        if (metric_type == M3GPU_METRIC_TIMER && plan.nq > 0 && n > 0) {
-            /* rank-select: each lane ranks elements lane, lane+64, ...
-             * LDS ops from one wave retire in order; the fences only stop
-             * compiler reordering around the cross-lane LDS use. */
-            __builtin_amdgcn_wave_barrier();
-            __threadfence_block();
-            for (uint32_t e = lane; e < n; e += WAVE) {
-                double v = qvals[e];
-                uint32_t rank = 0;
-                for (uint32_t j = 0; j < n; j++) {
-                    double o = qvals[j];
-                    rank += (o < v) || (o == v && j < e);
-                }
-                sorted[rank] = v;
-            }
-            __builtin_amdgcn_wave_barrier();
-            __threadfence_block();
-        }
-        if (lane < (uint32_t)plan.naggs) {
-            int32_t t = plan.agg_types[lane];
-            int8_t qi = plan.qidx[lane];
-            double r = 0;
-            if (metric_type == M3GPU_METRIC_COUNTER) { /* counter.go:112-131 */
-                switch (t) {
-                case M3GPU_AGG_MIN: r = (double)bs.imin; break;
-                case M3GPU_AGG_MAX: r = (double)bs.imax; break;
-                case M3GPU_AGG_MEAN: r = bs.count ? (double)bs.isum / (double)bs.count : 0; break;
-                case M3GPU_AGG_COUNT: r = (double)bs.count; break;
-                case M3GPU_AGG_SUM: r = (double)bs.isum; break;
-                case M3GPU_AGG_SUMSQ: r = (double)bs.isumsq; break;
-                case M3GPU_AGG_STDEV: r = m3_stdev(bs.count, (double)bs.isumsq, (double)bs.isum); break;
-                default: r = 0; break;
-                }
-            } else if (metric_type == M3GPU_METRIC_GAUGE) { /* gauge.go:144-165 */
-                switch (t) {
-                case M3GPU_AGG_LAST: r = bs.last; break;
-                case M3GPU_AGG_MIN: r = bs.fmin; break;
-                case M3GPU_AGG_MAX: r = bs.fmax; break;
-                case M3GPU_AGG_MEAN: r = bs.count ? bs.fsum / (double)bs.count : 0.0; break;
-                case M3GPU_AGG_COUNT: r = (double)bs.count; break;
-                case M3GPU_AGG_SUM: r = bs.fsum; break;
-                case M3GPU_AGG_SUMSQ: r = bs.fsumsq; break;
-                case M3GPU_AGG_STDEV: r = m3_stdev(bs.count, bs.fsumsq, bs.fsum); break;
-                default: r = 0; break;
-                }
-            } else { /* timer.go:131-153 */
-                if (qi >= 0) {
-                    if (n == 0) r = 0.0; /* empty stream Quantile -> 0 */
-                    else if (n <= 3) { /* quantilesFromBuf :210-229 */
-                        int idx = (int)(plan.qs[qi] * (double)n);
-                        if (idx >= (int)n) idx = n - 1;
-                        r = sorted[idx];
-                    } else {
-                        /* calcQuantiles walk closed form over the sorted
-                         * unique quantile list (one emission per sample) */
-                        int k = 0;
-                        for (int i = 0; i <= qi; i++) {
-                            int rank = (int)ceil(plan.qs[i] * (double)n);
-                            k = (i == 0) ? rank : ((rank > k + 1) ? rank : k + 1);
-                        }
-                        if (k > (int)n) k = n;
-                        r = sorted[k - 1];
-                    }
-                } else {
-                    switch (t) {
-                    case M3GPU_AGG_MIN: r = n ? sorted[0] : 0.0; break;   /* Quantile(0) */
-                    case M3GPU_AGG_MAX: r = n ? sorted[n - 1] : 0.0; break;
-                    case M3GPU_AGG_MEAN: r = bs.count ? bs.fsum / (double)bs.count : 0.0; break;
-                    case M3GPU_AGG_COUNT: r = (double)bs.count; break;
-                    case M3GPU_AGG_SUM: r = bs.fsum; break;
-                    case M3GPU_AGG_SUMSQ: r = bs.fsumsq; break;
-                    case M3GPU_AGG_STDEV: r = m3_stdev(bs.count, bs.fsumsq, bs.fsum); break;
-                    default: r = 0; break;
-                    }
-                }
-            }
-            out_row[(uint64_t)b * plan.naggs + lane] = r;
-        }
-    };
-
-    for (;;) {
-        int64_t t;
-        double v;
-        int rstat = d.next(&t, &v);
-        if (rstat < 0) { err = -rstat; break; }
-        bool have = rstat == 1;
-        int64_t b = -1;
-        if (have) {
-            if (cur_bucket < 0) base = (t / window_ns) * window_ns; /* Truncate */
-            if (t < base) { err = M3GPU_SERIES_UNSORTED; break; }
-            b = (t - base) / window_ns;
-            if (b >= (int64_t)nbuckets) { err = M3GPU_SERIES_CAPACITY; break; }
-            if (b < cur_bucket) { err = M3GPU_SERIES_UNSORTED; break; }
-        }
-        if (!have || b != cur_bucket) {
-            if (cur_bucket >= 0) emit_bucket(cur_bucket);
-            /* emit empty buckets in any gap (and the tail after the stream) */
-            int64_t stop = have ? b : (int64_t)nbuckets;
-            for (int64_t eb = (cur_bucket < 0 ? 0 : cur_bucket + 1); eb < stop; eb++) {
-                bs.reset();
-                nq_in_bucket = 0;
-                emit_bucket(eb);
-            }
-            if (!have) break;
-            bs.reset();
-            nq_in_bucket = 0;
-            cur_bucket = b;
-        }
-        /* accumulate */
-        if (metric_type == M3GPU_METRIC_COUNTER) { /* counter.go:52-78 */
-            int64_t iv = go_f2i(v);
-            bs.isum += iv;
-            bs.count++;
-            if (bs.imax < iv) bs.imax = iv;
-            if (bs.imin > iv) bs.imin = iv;
-            bs.isumsq += iv * iv;
-        } else if (metric_type == M3GPU_METRIC_GAUGE) { /* gauge.go:73-103 */
-            if (bs.last_at == 0 || t > bs.last_at) { bs.last_at = t; bs.last = v; }
-            bs.count++;
-            if (!isnan(v)) {
-                bs.fsum += v;
-                if (isnan(bs.fmax) || bs.fmax < v) bs.fmax = v;
-                if (isnan(bs.fmin) || bs.fmin > v) bs.fmin = v;
-                bs.fsumsq += v * v;
-            }
-        } else { /* timer.go:56-75 */
-            bs.count++;
-            bs.fsum += v;
-            bs.fsumsq += v * v;
-            if (plan.nq > 0) {
-                if (nq_in_bucket >= (uint32_t)plan.exact_cap ||
-                    nq_in_bucket >= QCAP) {
-                    err = M3GPU_SERIES_BUCKET_OVERFLOW;
-                    break;
-                }
-                if (lane == 0) qvals[nq_in_bucket] = v;
-                nq_in_bucket++;
-            }
-        }
-    }
-    if (lane == 0) out_errs[series] = err;
-}
-
 /* ===================== blob regather (layout pass) ===================== */
 /* Physically reorders packed streams: dst series i <- src series perm[i].
  * Used to lay the blob out in wave-schedule order (length-sorted), so the
@@ -2176,281 +1951,6 @@ k_compact(const uint8_t* __restrict__ src, uint32_t src_stride,
     for (uint32_t w = lane; w < nwords; w += WAVE) d[w] = s[w];
 }
 
-
-/* -------- series-per-lane fused rollup --------
- * Same semantics as k_rollup_batch but one series per LANE (64 parsers per
- * wave, like k_decode_batch). Timer quantile values stage in a per-lane LDS
- * row kept sorted by insertion (bucket sizes <= RQCAP_LANE); larger buckets
- * flag M3GPU_SERIES_BUCKET_OVERFLOW and the host retries those series on the
- * wave-per-series kernel (64-deep staging). */
-#define RQCAP_LANE 16
-
-#define RQ_NONE 0
-#define RQ_STAGED 1
-#define RQ_EXTREME 2
-
-template <int QMODE, int METRIC>
-__global__ void __launch_bounds__(BLOCK_THREADS, QMODE == RQ_STAGED ? 3 : 4)
-/* staged: 40KB LDS (qbuf + ring) pins 3 blocks/CU, so 3 waves/SIMD with no
-   spills; other modes target the 128-VGPR granule (4 waves/SIMD) */
-k_rollup_lane(const uint8_t* __restrict__ blobs,
-              const uint64_t* __restrict__ offsets,
-              const uint32_t* __restrict__ lens,
-              uint32_t nseries, int int_optimized, uint8_t default_unit,
-              int64_t window_ns, uint32_t nbuckets,
-              RollupPlan plan,
-              double* __restrict__ out, int64_t* __restrict__ out_window_ts,
-              int32_t* __restrict__ out_errs) {
-    const uint32_t lane = threadIdx.x & (WAVE - 1);
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t series = blockIdx.x * BLOCK_THREADS + wave * WAVE + lane;
-
-    constexpr bool WITH_Q = QMODE == RQ_STAGED;
-    __shared__ double qbuf_all[WITH_Q ? WAVES_PER_BLOCK : 1]
-                              [WITH_Q ? WAVE : 1][WITH_Q ? RQCAP_LANE : 1];
-    double* qrow = WITH_Q ? qbuf_all[wave][lane] : nullptr;
-    /* per-lane input ring, as in k_decode_batch */
-    __shared__ uint64_t rring_all[WAVES_PER_BLOCK][WAVE][IN_STRIDE];
-    uint64_t* rring = rring_all[wave][lane];
-
-    const bool in_range = series < nseries;
-    RingDecoder d;
-    d.init(blobs, in_range ? offsets[series] : 0, in_range ? lens[series] : 0,
-           int_optimized != 0, default_unit, rring);
-
-    double* out_row = out + (uint64_t)series * nbuckets * plan.naggs;
-    int64_t* wts_row = out_window_ts ? out_window_ts + (uint64_t)series * nbuckets : nullptr;
-
-    BucketState bs;
-    bs.reset();
-    int64_t base = 0;
-    int64_t cur_bucket = -1;
-    int64_t cur_lo = 0, cur_hi = 0; /* current bucket ts bounds */
-    uint32_t nq = 0;
-    int err = 0;
-    bool running = in_range;
-
-    auto emit_bucket = [&](int64_t b) {
-        if (b < 0 || b >= (int64_t)nbuckets) return;
-        if (wts_row) wts_row[b] = base + (b + 1) * window_ns;
-        /* even naggs: emit value pairs as aligned 16B stores (the rows are
-         * naggs*8B apart, so paired stores halve the line-granular write
-         * amplification of the scattered per-lane emission) */
-        const bool paired = (plan.naggs & 1) == 0;
-        double pend = 0;
-        for (int k = 0; k < plan.naggs; k++) {
-            int32_t t = plan.agg_types[k];
-            int8_t qi = plan.qidx[k];
-            double r = 0;
-            if (METRIC == M3GPU_METRIC_COUNTER) { /* counter.go:112-131 */
-                switch (t) {
-                case M3GPU_AGG_MIN: r = (double)bs.imin; break;
-                case M3GPU_AGG_MAX: r = (double)bs.imax; break;
-                case M3GPU_AGG_MEAN: r = bs.count ? (double)bs.isum / (double)bs.count : 0; break;
-                case M3GPU_AGG_COUNT: r = (double)bs.count; break;
-                case M3GPU_AGG_SUM: r = (double)bs.isum; break;
-                case M3GPU_AGG_SUMSQ: r = (double)bs.isumsq; break;
-                case M3GPU_AGG_STDEV: r = m3_stdev(bs.count, (double)bs.isumsq, (double)bs.isum); break;
-                default: break;
-                }
-            } else if (METRIC == M3GPU_METRIC_GAUGE) { /* gauge.go:144-165 */
-                switch (t) {
-                case M3GPU_AGG_LAST: r = bs.last; break;
-                case M3GPU_AGG_MIN: r = bs.fmin; break;
-                case M3GPU_AGG_MAX: r = bs.fmax; break;
-                case M3GPU_AGG_MEAN: r = bs.count ? bs.fsum / (double)bs.count : 0.0; break;
-                case M3GPU_AGG_COUNT: r = (double)bs.count; break;
-                case M3GPU_AGG_SUM: r = bs.fsum; break;
-                case M3GPU_AGG_SUMSQ: r = bs.fsumsq; break;
-                case M3GPU_AGG_STDEV: r = m3_stdev(bs.count, bs.fsumsq, bs.fsum); break;
-                default: break;
-                }
-            } else { /* timer.go:131-153; qrow holds the sorted bucket values */
-                if (QMODE == RQ_EXTREME && qi >= 0) {
-                    /* all-high quantile set: every requested quantile
-                     * resolves to the bucket max for n <= plan.extreme_cap
-                     * (host-verified against the walk AND quantilesFromBuf;
-                     * deeper buckets took the overflow path) */
-                    r = bs.count ? bs.fmax : 0.0;
-                } else if (WITH_Q && qi >= 0) {
-                    if (nq == 0) r = 0.0; /* empty stream Quantile -> 0 */
-                    else if (nq <= 3) { /* quantilesFromBuf :210-229 */
-                        uint32_t idx = (uint32_t)(plan.qs[qi] * (double)nq);
-                        if (idx >= nq) idx = nq - 1;
-                        r = qrow[idx];
-                    } else { /* calcQuantiles walk closed form */
-                        int kk = 0;
-                        for (int i = 0; i <= qi; i++) {
-                            int rank = (int)ceil(plan.qs[i] * (double)nq);
-                            kk = (i == 0) ? rank : ((rank > kk + 1) ? rank : kk + 1);
-                        }
-                        if (kk > (int)nq) kk = nq;
-                        r = qrow[kk - 1];
-                    }
-                } else {
-                    switch (t) {
-                    case M3GPU_AGG_MIN:
-                        r = (QMODE == RQ_EXTREME)
-                                ? (bs.count ? bs.fmin : 0.0)
-                                : ((WITH_Q && nq) ? qrow[0] : 0.0);
-                        break;
-                    case M3GPU_AGG_MAX:
-                        r = (QMODE == RQ_EXTREME)
-                                ? (bs.count ? bs.fmax : 0.0)
-                                : ((WITH_Q && nq) ? qrow[nq - 1] : 0.0);
-                        break;
-                    case M3GPU_AGG_MEAN: r = bs.count ? bs.fsum / (double)bs.count : 0.0; break;
-                    case M3GPU_AGG_COUNT: r = (double)bs.count; break;
-                    case M3GPU_AGG_SUM: r = bs.fsum; break;
-                    case M3GPU_AGG_SUMSQ: r = bs.fsumsq; break;
-                    case M3GPU_AGG_STDEV: r = m3_stdev(bs.count, bs.fsumsq, bs.fsum); break;
-                    default: break;
-                    }
-                }
-            }
-            if (paired) {
-                if (k & 1) {
-                    double2 pr;
-                    pr.x = pend;
-                    pr.y = r;
-                    *(double2*)(out_row + (uint64_t)b * plan.naggs + k - 1) = pr;
-                } else {
-                    pend = r;
-                }
-            } else {
-                out_row[(uint64_t)b * plan.naggs + k] = r;
-            }
-        }
-    };
-
-    while (__any(running)) {
-        const RingPending pd = d.r.refill_issue(running);
-#pragma unroll 1
-        for (uint32_t jt = 0; jt < RF_SPAN; jt++) {
-        if (running) {
-            int64_t t;
-            double v;
-            int rstat = d.next(&t, &v);
-            if (rstat < 0) {
-                err = -rstat;
-                running = false;
-            } else {
-                bool have = rstat == 1;
-                int64_t b = -1;
-                bool ok = true;
-                if (have) {
-                    if (cur_bucket >= 0 && t >= cur_lo && t < cur_hi) {
-                        /* same bucket: two compares instead of a 64-bit
-                         * division per point */
-                        b = cur_bucket;
-                    } else {
-                        if (cur_bucket < 0) base = (t / window_ns) * window_ns; /* Truncate */
-                        if (t < base) { err = M3GPU_SERIES_UNSORTED; running = false; ok = false; }
-                        else {
-                            b = (t - base) / window_ns;
-                            if (b >= (int64_t)nbuckets) { err = M3GPU_SERIES_CAPACITY; running = false; ok = false; }
-                            else if (b < cur_bucket) { err = M3GPU_SERIES_UNSORTED; running = false; ok = false; }
-                        }
-                    }
-                }
-                if (ok && (!have || b != cur_bucket)) {
-                    if (cur_bucket >= 0) emit_bucket(cur_bucket);
-                    int64_t stop = have ? b : (int64_t)nbuckets;
-                    for (int64_t eb = (cur_bucket < 0 ? 0 : cur_bucket + 1); eb < stop; eb++) {
-                        bs.reset();
-                        nq = 0;
-                        emit_bucket(eb);
-                    }
-                    if (!have) { running = false; ok = false; }
-                    else {
-                        bs.reset();
-                        nq = 0;
-                        cur_bucket = b;
-                        cur_lo = base + b * window_ns;
-                        cur_hi = cur_lo + window_ns;
-                    }
-                }
-                if (ok) {
-                    if (METRIC == M3GPU_METRIC_COUNTER) { /* counter.go:52-78 */
-                        int64_t iv = go_f2i(v);
-                        bs.isum += iv;
-                        bs.count++;
-                        if (bs.imax < iv) bs.imax = iv;
-                        if (bs.imin > iv) bs.imin = iv;
-                        bs.isumsq += iv * iv;
-                    } else if (METRIC == M3GPU_METRIC_GAUGE) { /* gauge.go:73-103 */
-                        if (bs.last_at == 0 || t > bs.last_at) { bs.last_at = t; bs.last = v; }
-                        bs.count++;
-                        if (!isnan(v)) {
-                            bs.fsum += v;
-                            if (isnan(bs.fmax) || bs.fmax < v) bs.fmax = v;
-                            if (isnan(bs.fmin) || bs.fmin > v) bs.fmin = v;
-                            bs.fsumsq += v * v;
-                        }
-                    } else { /* timer.go:56-75 */
-                        if (QMODE == RQ_EXTREME &&
-                            (isnan(v) ||
-                             bs.count >= (int64_t)plan.extreme_cap)) {
-                            /* NaN ordering and deep buckets keep the exact
-                             * staged semantics: retry on the wave tier */
-                            err = M3GPU_SERIES_BUCKET_OVERFLOW;
-                            running = false;
-                        } else {
-                            if (QMODE == RQ_EXTREME) {
-                                if (bs.count == 0) {
-                                    bs.fmin = v;
-                                    bs.fmax = v;
-                                } else {
-                                    if (v < bs.fmin) bs.fmin = v;
-                                    if (v > bs.fmax) bs.fmax = v;
-                                }
-                            }
-                            bs.count++;
-                            bs.fsum += v;
-                            bs.fsumsq += v * v;
-                            if (WITH_Q && plan.nq > 0) {
-                                if (nq >= RQCAP_LANE ||
-                                    nq >= (uint32_t)plan.exact_cap) {
-                                    err = M3GPU_SERIES_BUCKET_OVERFLOW;
-                                    running = false;
-                                    bs.count--; /* not accumulated */
-                                } else {
-                                    /* insertion into this lane's sorted row */
-                                    uint32_t j = nq;
-                                    while (j > 0 && qrow[j - 1] > v) { qrow[j] = qrow[j - 1]; j--; }
-                                    qrow[j] = v;
-                                    nq++;
-                                }
-                            }
-                        }
-                    }
-                }
-            }
-        }
-        }
-        d.r.refill_commit(pd);
-    }
-    if (in_range) out_errs[series] = err;
-}
-
-
-__global__ void __launch_bounds__(BLOCK_THREADS)
-k_count_errcode(const int32_t* __restrict__ errs, uint32_t n, int32_t code,
-                uint32_t* __restrict__ out) {
-    /* grid-stride count of one per-series error code: lets the rollup
-     * dispatch test for tier retries with a 4-byte D2H instead of pulling
-     * and scanning the whole error array every call */
-    uint32_t cnt = 0;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
-         i += gridDim.x * blockDim.x)
-        if (errs[i] == code) cnt++;
-    if (__any(cnt != 0)) {
-        cnt += __shfl_down(cnt, 32); cnt += __shfl_down(cnt, 16);
-        cnt += __shfl_down(cnt, 8); cnt += __shfl_down(cnt, 4);
-        cnt += __shfl_down(cnt, 2); cnt += __shfl_down(cnt, 1);
-        if ((threadIdx.x & (WAVE - 1)) == 0 && cnt) atomicAdd(out, cnt);
-    }
-}
 
 /* ===================== replica-deduplicating merge =====================
  * MultiReaderIterator semantics over one slice of R (<=4) replica rows of
@@ -3422,403 +2922,10 @@ k_step_fused(const uint8_t* __restrict__ blobs,
     }
 }
 
-
-/* ===================== full-CKMS deep-bucket rollup =====================
- * Third tier of the timer-quantile chain (after the per-lane <=16 staging
- * and the wave-kernel exact-order-statistics cap): the reference CKMS
- * stream WITH compression (quantile/cm/stream.go:77-429), ported from the
- * oracle's restatement onto LDS arrays. One WAVE per workgroup, one series
- * per workgroup (rare retry path; correctness, not throughput):
- *  - samples double-buffer (value,numRanks,delta) replaces the linked list;
- *    the insert cursor walk becomes a two-pointer merge (equivalent:
- *    incoming v inserted before the first list element with value >= v,
- *    delta = that element's numRanks+delta-1; the tail appends delta 0);
- *  - compress walks backward tracking the surviving next element; removed
- *    samples are compacted after the walk (same removal order);
- *  - in the AddBatch(1)/Flush usage the compress cursor is always nil on
- *    insert entry, so the compValue/compressMinRank-in-insert branch of the
- *    reference is dead (stream.go:284-287,303) and omitted;
- *  - buffers bufLess/bufMore are value MULTISETS here (the reference's heap
- *    order only permutes ties, which insert() cannot distinguish);
- *  - capacity overflow (sample list or buffer > CKMS_CAP) flags
- *    M3GPU_SERIES_BUCKET_OVERFLOW — never an approximation. */
-#define CKMS_CAP 3072
-#define CKMS_BUF 2080 /* bufMore peak = carried bufLess (<=1024) + 1024 new */
-
-struct CkmsLds {
-    double* val[2];
-    int32_t* nr[2];
-    int32_t* dl[2];
-    double* less;
-    double* more;
-};
-
-struct CkmsState {
-    int cur;           /* active buffer index */
-    int32_t len;       /* samples */
-    int32_t nless, nmore;
-    int64_t num_values;
-    int32_t counter;   /* insertAndCompressCounter */
-    int err;
-};
-
-__device__ __forceinline__ void ckms_reset(CkmsState& st) {
-    st.cur = 0;
-    st.len = 0;
-    st.nless = 0;
-    st.nmore = 0;
-    st.num_values = 0;
-    st.counter = 0;
-}
-
-/* wave-parallel ascending sort of buf[0..n) into tmp[0..n) (rank-select) */
-__device__ __forceinline__ void ckms_sort(const double* buf, double* tmp,
-                                          int32_t n, uint32_t lane) {
-    __builtin_amdgcn_wave_barrier();
-    __threadfence_block();
-    for (int32_t e = lane; e < n; e += WAVE) {
-        double v = buf[e];
-        int32_t rank = 0;
-        for (int32_t j = 0; j < n; j++) {
-            double o = buf[j];
-            rank += (o < v) || (o == v && j < e);
-        }
-        tmp[rank] = v;
-    }
-    __builtin_amdgcn_wave_barrier();
-    __threadfence_block();
-}
-
-/* stream.go:362-377 threshold(rank), exact int64 truncation */
-__device__ __forceinline__ int64_t ckms_threshold(const RollupPlan& plan,
-                                                  int64_t num_vals, int64_t rank) {
-    int64_t min_val = INT64_MAX;
-    double eps = 2.0 * plan.eps;
-    for (int i = 0; i < plan.nq; i++) {
-        int64_t qmin;
-        if (rank >= (int64_t)(plan.qs[i] * (double)num_vals))
-            qmin = (int64_t)(eps * (double)rank / plan.qs[i]);
-        else
-            qmin = (int64_t)(eps * (double)(num_vals - rank) / (1.0 - plan.qs[i]));
-        if (qmin < min_val) min_val = qmin;
-    }
-    return min_val;
-}
-
-/* insert sorted batch (stream.go:280-331) + compress (:333-401); lane 0
- * does the sequential merge/walk, the wave sorts. `sorted` is dedicated LDS scratch. */
-__device__ void ckms_insert_compress(CkmsLds& L, CkmsState& st,
-                                     const RollupPlan& plan, double* sorted,
-                                     uint32_t lane) {
-    int32_t m = st.nmore;
-    ckms_sort(L.more, sorted, m, lane);
-    if (st.len + m > CKMS_CAP) { /* uniform: all lanes see the same state */
-        st.err = M3GPU_SERIES_BUCKET_OVERFLOW;
-        return;
-    }
-    if (lane == 0) {
-        int src = st.cur, dst = st.cur ^ 1;
-        int32_t n = st.len;
-        {
-            /* two-pointer merge == the reference's cursor walk */
-            int32_t i = 0, j = 0, o = 0;
-            while (i < n) {
-                if (j < m && sorted[j] <= L.val[src][i]) {
-                    L.val[dst][o] = sorted[j];
-                    L.nr[dst][o] = 1;
-                    L.dl[dst][o] = L.nr[src][i] + L.dl[src][i] - 1;
-                    o++; j++;
-                } else {
-                    L.val[dst][o] = L.val[src][i];
-                    L.nr[dst][o] = L.nr[src][i];
-                    L.dl[dst][o] = L.dl[src][i];
-                    o++; i++;
-                }
-            }
-            while (j < m) { /* PushBack tail, delta 0 (:316-328) */
-                L.val[dst][o] = sorted[j];
-                L.nr[dst][o] = 1;
-                L.dl[dst][o] = 0;
-                o++; j++;
-            }
-            st.cur = dst;
-            st.len = o;
-            st.num_values += m;
-            /* compress (:333-401); entry cursor nil in this usage */
-            int32_t len = st.len;
-            if (len >= 3) {
-                int b = st.cur;
-                int64_t cmr = st.num_values - 1 - L.nr[b][len - 2];
-                int32_t nxt = len - 2; /* surviving element after curr */
-                for (int32_t c = len - 3; c >= 1; c--) {
-                    int64_t max_rank = cmr + L.nr[b][c] + L.dl[b][c];
-                    int64_t thr = ckms_threshold(plan, st.num_values, max_rank);
-                    cmr -= L.nr[b][c];
-                    int64_t test_val = L.nr[b][c] + L.nr[b][nxt] + L.dl[b][nxt];
-                    if (test_val <= thr) {
-                        L.nr[b][nxt] += L.nr[b][c];
-                        L.nr[b][c] = -1; /* removed mark */
-                    } else {
-                        nxt = c;
-                    }
-                }
-                /* compact, preserving order */
-                int32_t o2 = 0;
-                for (int32_t c = 0; c < len; c++) {
-                    if (L.nr[b][c] >= 0) {
-                        if (o2 != c) {
-                            L.val[b][o2] = L.val[b][c];
-                            L.nr[b][o2] = L.nr[b][c];
-                            L.dl[b][o2] = L.dl[b][c];
-                        }
-                        o2++;
-                    }
-                }
-                st.len = o2;
-            }
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    __threadfence_block();
-    /* uniform parts every lane must perform itself: the buffer swap
-     * (resetInsertCursor, stream.go:425-429) swaps POINTERS held per lane */
-    double* t = L.less; L.less = L.more; L.more = t;
-    st.nmore = st.nless;
-    st.nless = 0;
-    /* lane-0-computed scalars: broadcast via readfirstlane */
-    st.cur = __builtin_amdgcn_readfirstlane(st.cur);
-    st.len = __builtin_amdgcn_readfirstlane(st.len);
-    st.num_values = ((int64_t)(uint32_t)__builtin_amdgcn_readfirstlane(
-                         (uint32_t)(st.num_values >> 32)) << 32) |
-                    (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)st.num_values);
-}
-
-/* stream.go:77-116 AddBatch(values[0..1)) — one value at a time, exactly
- * like Timer.AddBatch -> stream per-value adds in the rollup loop. */
-__device__ __forceinline__ void ckms_add(CkmsLds& L, CkmsState& st,
-                                         const RollupPlan& plan, double v,
-                                         double* sorted, uint32_t lane) {
-    if (st.err) return;
-    if (st.len == 0 && st.nmore == 0 && st.nless == 0 && st.num_values == 0) {
-        /* first value becomes the first sample (:88-97) */
-        if (lane == 0) {
-            L.val[st.cur][0] = v;
-            L.nr[st.cur][0] = 1;
-            L.dl[st.cur][0] = 0;
-        }
-        st.len = 1;
-        st.num_values = 1;
-        __builtin_amdgcn_wave_barrier();
-        __threadfence_block();
-        return;
-    }
-    double insert_point = L.val[st.cur][0]; /* insertCursor == head here */
-    if (st.nless >= CKMS_BUF || st.nmore >= CKMS_BUF) {
-        st.err = M3GPU_SERIES_BUCKET_OVERFLOW;
-        return;
-    }
-    if (v < insert_point) {
-        if (lane == 0) L.less[st.nless] = v;
-        st.nless++;
-    } else {
-        if (lane == 0) L.more[st.nmore] = v;
-        st.nmore++;
-    }
-    __builtin_amdgcn_wave_barrier();
-    __threadfence_block();
-    if (st.counter == plan.every) { /* insertAndCompressEvery, checked BEFORE ++ */
-        ckms_insert_compress(L, st, plan, sorted, lane);
-        st.counter = 0;
-    }
-    st.counter++;
-}
-
-/* stream.go:123-137 Flush */
-__device__ __forceinline__ void ckms_flush(CkmsLds& L, CkmsState& st,
-                                           const RollupPlan& plan,
-                                           double* sorted, uint32_t lane) {
-    while (!st.err && (st.nless > 0 || st.nmore > 0)) {
-        if (st.nmore == 0) { /* resetInsertCursor: swap */
-            double* t = L.less; L.less = L.more; L.more = t;
-            st.nmore = st.nless;
-            st.nless = 0;
-        }
-        ckms_insert_compress(L, st, plan, sorted, lane);
-    }
-}
-
-/* stream.go:231-277 calcQuantiles (+ :210-229 quantilesFromBuf), filling
- * computed[0..nq) for the plan's sorted unique quantile list. computed[]
- * must be zeroed per bucket first: the reference leaves un-emitted
- * quantiles at the zero value (the post-loop condition can fail for the
- * top quantiles at certain numValues — real behavior, preserved). Lane 0
- * only; thr_rank/thr_thresh are LDS scratch (>= plan.nq entries). */
-__device__ void ckms_calc_quantiles(const CkmsLds& L, const CkmsState& st,
-                                    const RollupPlan& plan, double* computed,
-                                    int64_t* thr_rank, int64_t* thr_thresh) {
-    if (plan.nq == 0 || st.num_values == 0) return;
-    const int b = st.cur;
-    if (st.num_values <= 3) { /* quantilesFromBuf over the sample list */
-        for (int i = 0; i < plan.nq; i++) {
-            int32_t idx = (int32_t)(plan.qs[i] * (double)st.len);
-            if (idx >= st.len) idx = st.len - 1;
-            computed[i] = L.val[b][idx];
-        }
-        return;
-    }
-    for (int i = 0; i < plan.nq; i++) {
-        int64_t rank = (int64_t)ceil(plan.qs[i] * (double)st.num_values);
-        thr_rank[i] = rank;
-        thr_thresh[i] =
-            (int64_t)ceil((double)ckms_threshold(plan, st.num_values, rank) / 2.0);
-    }
-    int64_t min_rank = 0, max_rank = 0;
-    int idx = 0;
-    int32_t prev = 0;
-    for (int32_t c = 0; c < st.len && idx < plan.nq; c++) {
-        max_rank = min_rank + L.nr[b][c] + L.dl[b][c];
-        if (max_rank > thr_rank[idx] + thr_thresh[idx] || min_rank > thr_rank[idx]) {
-            computed[idx] = L.val[b][prev];
-            idx++;
-        }
-        min_rank += L.nr[b][c];
-        prev = c;
-    }
-    for (int i = idx; i < plan.nq; i++) { /* post-loop (:268-276), note >= */
-        if (max_rank >= thr_rank[i] + thr_thresh[i] || min_rank > thr_rank[i])
-            computed[i] = L.val[b][prev];
-    }
-}
-
-/* ------------- the deep-bucket rollup kernel (third tier) -------------
- * One series per 64-thread workgroup (one wave), full 150 KB dynamic LDS
- * for the CKMS state. Only TIMER series with quantile aggs can reach this
- * tier (nothing else sets BUCKET_OVERFLOW). Decode/bucket walk identical
- * to k_rollup_batch. */
-#define CKMS_BLOCK 64
-
-__global__ void __launch_bounds__(CKMS_BLOCK)
-k_rollup_ckms(const uint8_t* __restrict__ blobs,
-              const uint64_t* __restrict__ offsets,
-              const uint32_t* __restrict__ lens,
-              const int32_t* __restrict__ select, uint32_t nseries,
-              int int_optimized, uint8_t default_unit,
-              int64_t window_ns, uint32_t nbuckets, RollupPlan plan,
-              double* __restrict__ out, int64_t* __restrict__ out_window_ts,
-              int32_t* __restrict__ out_errs) {
-    extern __shared__ uint8_t lds_raw[];
-    const uint32_t lane = threadIdx.x % WAVE;
-    const uint32_t slot = blockIdx.x;
-    if (slot >= nseries) return;
-    const uint32_t series = __builtin_amdgcn_readfirstlane(
-        select ? (uint32_t)select[slot] : slot);
-
-    /* carve the dynamic LDS (layout mirrored by rollup_ckms_lds_bytes) */
-    uint8_t* p = lds_raw;
-    CkmsLds L;
-    L.val[0] = (double*)p; p += CKMS_CAP * 8;
-    L.val[1] = (double*)p; p += CKMS_CAP * 8;
-    L.nr[0] = (int32_t*)p; p += CKMS_CAP * 4;
-    L.nr[1] = (int32_t*)p; p += CKMS_CAP * 4;
-    L.dl[0] = (int32_t*)p; p += CKMS_CAP * 4;
-    L.dl[1] = (int32_t*)p; p += CKMS_CAP * 4;
-    L.less = (double*)p; p += CKMS_BUF * 8;
-    L.more = (double*)p; p += CKMS_BUF * 8;
-    double* sorted = (double*)p; p += CKMS_BUF * 8;
-    double* computed = (double*)p; p += MAX_AGGS * 8;
-    int64_t* thr_rank = (int64_t*)p; p += MAX_AGGS * 8;
-    int64_t* thr_thresh = (int64_t*)p; p += MAX_AGGS * 8;
-
-    Decoder d;
-    d.init(blobs, offsets[series], lens[series], int_optimized != 0, default_unit);
-
-    double* out_row = out + (uint64_t)series * nbuckets * plan.naggs;
-    int64_t* wts_row = out_window_ts ? out_window_ts + (uint64_t)series * nbuckets : nullptr;
-
-    BucketState bs;
-    bs.reset();
-    CkmsState st;
-    ckms_reset(st);
-    st.err = 0;
-    int64_t base = 0;
-    int64_t cur_bucket = -1;
-    int err = 0;
-
-    auto emit_bucket = [&](int64_t bk) {
-        if (bk < 0 || bk >= (int64_t)nbuckets) return;
-        if (wts_row && lane == 0) wts_row[bk] = base + (bk + 1) * window_ns;
-        ckms_flush(L, st, plan, sorted, lane);
-        if (st.err) return;
-        if (lane == 0) {
-            for (int i = 0; i < plan.nq; i++) computed[i] = 0.0;
-            ckms_calc_quantiles(L, st, plan, computed, thr_rank, thr_thresh);
-        }
-        __builtin_amdgcn_wave_barrier();
-        __threadfence_block();
-        if (lane < (uint32_t)plan.naggs) { /* timer.go:131-153 ValueOf */
-            int32_t t = plan.agg_types[lane];
-            int8_t qi = plan.qidx[lane];
-            double r = 0;
-            int cb = st.cur;
-            if (qi >= 0) {
-                r = st.len ? computed[qi] : 0.0; /* Quantile(q): computed */
-            } else {
-                switch (t) {
-                case M3GPU_AGG_MIN: r = st.len ? L.val[cb][0] : 0.0; break;
-                case M3GPU_AGG_MAX: r = st.len ? L.val[cb][st.len - 1] : 0.0; break;
-                case M3GPU_AGG_MEAN: r = bs.count ? bs.fsum / (double)bs.count : 0.0; break;
-                case M3GPU_AGG_COUNT: r = (double)bs.count; break;
-                case M3GPU_AGG_SUM: r = bs.fsum; break;
-                case M3GPU_AGG_SUMSQ: r = bs.fsumsq; break;
-                case M3GPU_AGG_STDEV: r = m3_stdev(bs.count, bs.fsumsq, bs.fsum); break;
-                default: r = 0; break;
-                }
-            }
-            out_row[(uint64_t)bk * plan.naggs + lane] = r;
-        }
-    };
-
-    for (;;) {
-        int64_t t;
-        double v;
-        int rstat = d.next(&t, &v);
-        if (rstat < 0) { err = -rstat; break; }
-        bool have = rstat == 1;
-        int64_t b = -1;
-        if (have) {
-            if (cur_bucket < 0) base = (t / window_ns) * window_ns;
-            if (t < base) { err = M3GPU_SERIES_UNSORTED; break; }
-            b = (t - base) / window_ns;
-            if (b >= (int64_t)nbuckets) { err = M3GPU_SERIES_CAPACITY; break; }
-            if (b < cur_bucket) { err = M3GPU_SERIES_UNSORTED; break; }
-        }
-        if (!have || b != cur_bucket) {
-            if (cur_bucket >= 0) {
-                emit_bucket(cur_bucket);
-                if (st.err) { err = st.err; break; }
-            }
-            int64_t stop = have ? b : (int64_t)nbuckets;
-            for (int64_t eb = (cur_bucket < 0 ? 0 : cur_bucket + 1); eb < stop; eb++) {
-                bs.reset();
-                ckms_reset(st);
-                emit_bucket(eb);
-            }
-            if (!have) break;
-            bs.reset();
-            ckms_reset(st);
-            cur_bucket = b;
-        }
-        /* timer.go:56-75 AddBatch, one value at a time */
-        bs.count++;
-        bs.fsum += v;
-        bs.fsumsq += v * v;
-        ckms_add(L, st, plan, v, sorted, lane);
-        if (st.err) { err = st.err; break; }
-    }
-    if (lane == 0) out_errs[series] = err;
-}
-
 } // namespace m3
+
+/* ===================== fused decode -> rollup kernels ===================== */
+#include "rollup_kernels.h" /* all three tiers, over the decoders above */
 
 /* ============================ C-ABI host layer ============================ */
 
@@ -4188,24 +3295,22 @@ int m3gpu_rollup_batch_dev_opts(
 
     /* One retry tier: rerun the series still flagged as overflowed on the
      * wave-per-series kernel, or (ckms) on the real compressed CKMS
-     * (k_rollup_ckms, one series per workgroup, ~122 KB dynamic LDS), and
+     * (k_rollup_ckms, one series per workgroup, ~145 KB dynamic LDS), and
      * wait for it, since the next step reads the flags it rewrites. */
     auto run_tier = [&](bool ckms) -> int {
         DevBuf<int32_t> sel;
         uint32_t n = 0;
         int rc = collect_overflow(d_out_errs, nseries, &sel, &n);
         if (rc != M3GPU_OK || n == 0) return rc;
-        if (!ckms) {
+        if (!ckms) { /* timers with quantiles only: with_q holds here */
             hipLaunchKernelGGL(m3::k_rollup_batch, dim3(grid_for(n)),
                                dim3(BLOCK_THREADS), 0, s,
                                d_blobs, d_offsets, d_lens, sel.p, n,
-                               int_optimized, default_unit, metric_type,
+                               int_optimized, default_unit,
                                window_ns, nbuckets, plan,
                                d_out, d_out_window_ts, d_out_errs);
         } else {
-            size_t lds_bytes = (size_t)CKMS_CAP * 32 /* val+nr+dl x2 */
-                             + (size_t)CKMS_BUF * 24 /* less+more+sorted */
-                             + (size_t)MAX_AGGS * 24; /* computed+thr */
+            size_t lds_bytes = m3::CkmsLdsLayout::bytes;
             HIP_TRY(hipFuncSetAttribute(
                 reinterpret_cast<const void*>(m3::k_rollup_ckms),
                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));

@@ -1,7 +1,8 @@
 /*
- * rollup_plan.h — the rollup kernels' by-value plan argument and the host
- * code that fills it in. Plain C++17, no HIP header: the builder is host
- * only and is compiled on its own by tests/rollup_plan_driver.cpp.
+ * rollup_plan.h — the rollup kernels' by-value plan argument, the host code
+ * that fills it in, and the exact-quantile index that the builder and the
+ * kernels share. Plain C++17, no HIP header: it is compiled on its own by
+ * tests/rollup_plan_driver.cpp.
  */
 #ifndef M3_ROLLUP_PLAN_H
 #define M3_ROLLUP_PLAN_H
@@ -14,6 +15,15 @@
 
 #define QCAP 512 /* wave-kernel LDS staging capacity per series */
 #define MAX_AGGS 16
+
+/* shared by host code and kernels: host+device under hipcc, plain otherwise */
+#ifdef __HIPCC__
+#define M3_HD __host__ __device__
+#define M3_INLINE __forceinline__
+#else
+#define M3_HD
+#define M3_INLINE inline
+#endif
 
 namespace m3 {
 
@@ -62,6 +72,24 @@ static inline double agg_quantile_of_host(int32_t t) {
     case M3GPU_AGG_P9999: return 0.9999;
     default: return -1.0;
     }
+}
+
+/* 0-based index into a bucket's n >= 1 sorted values of quantile qs[qi] of
+ * the sorted unique list qs, while the CKMS stream never compresses
+ * (n <= exact_cap): quantilesFromBuf (stream.go:210-229) for n <= 3, else
+ * the closed form of the calcQuantiles walk (:231-277), which emits one
+ * sample per quantile: k_i = max(ceil(q_i*n), k_{i-1}+1), index min(k,n)-1. */
+M3_HD static M3_INLINE int exact_quantile_index(const double* qs, int qi, int n) {
+    if (n <= 3) {
+        int idx = (int)(qs[qi] * (double)n);
+        return idx < n ? idx : n - 1;
+    }
+    int k = 0;
+    for (int i = 0; i <= qi; i++) {
+        int rank = (int)ceil(qs[i] * (double)n);
+        k = (i == 0) ? rank : ((rank > k + 1) ? rank : k + 1);
+    }
+    return (k < n ? k : n) - 1;
 }
 
 /* Fill *plan for naggs <= MAX_AGGS aggregation types (the caller bounds
@@ -124,31 +152,17 @@ static inline void rollup_plan_build(const int32_t* agg_types, int naggs,
         if (merges) { plan->exact_cap = v - 1; break; }
     }
     /* extreme_cap: largest n (bounded by exact_cap) for which EVERY
-     * requested quantile resolves to sorted[n-1] — the bucket max — in
-     * BOTH regimes the lane kernel reproduces (quantilesFromBuf for n<=3,
-     * the calcQuantiles walk with the k_{i-1}+1 shift above). All-high
-     * quantile sets (p90+, e.g. the sum/min/max/p99 rollup) then need no
-     * per-point value staging at all: running min/max suffice. */
+     * requested quantile resolves to sorted[n-1] — the bucket max — by
+     * exact_quantile_index, the same function the kernels index with.
+     * All-high quantile sets (p90+, e.g. the sum/min/max/p99 rollup) then
+     * need no per-point value staging at all: running min/max suffice. */
     plan->extreme_cap = 0;
     if (nq > 0) {
         int capn = plan->exact_cap < QCAP ? plan->exact_cap : QCAP;
         for (int n = 1; n <= capn; n++) {
             bool allmax = true;
-            if (n <= 3) {
-                for (int i = 0; i < nq && allmax; i++) {
-                    int idx = (int)(qs[i] * (double)n);
-                    if (idx >= n) idx = n - 1;
-                    if (idx != n - 1) allmax = false;
-                }
-            } else {
-                int kk = 0;
-                for (int i = 0; i < nq; i++) {
-                    int rank = (int)ceil(qs[i] * (double)n);
-                    kk = (i == 0) ? rank : ((rank > kk + 1) ? rank : kk + 1);
-                    int kc = kk > n ? n : kk;
-                    if (kc != n) { allmax = false; break; }
-                }
-            }
+            for (int i = 0; i < nq && allmax; i++)
+                allmax = exact_quantile_index(qs, i, n) == n - 1;
             if (!allmax) break;
             plan->extreme_cap = n;
         }

@@ -2,14 +2,22 @@
 extreme_cap) on the CPU: tests/rollup_plan_driver.cpp is compiled as a
 stand-alone program with the address and undefined-behaviour sanitizers, run
 as a child process, and every field is compared with a python restatement of
-the documented rules."""
+the documented rules.
+
+The same driver holds what the rollup kernels share with the host: the
+exact-quantile index (rollup_plan.h) against a python restatement, and the
+bucket accumulate and ValueOf (rollup_bucket.h) against the oracle's rollup
+of single buckets."""
 import json
 import math
 import os
 import shutil
 import subprocess
 
+import numpy as np
 import pytest
+
+import oracle
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 QCAP = 512
@@ -23,7 +31,7 @@ QUANTILE = dict(median=0.5, p10=0.1, p20=0.2, p25=0.25, p30=0.3, p40=0.4,
 
 
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
+def driver_exe(tmp_path_factory):
     gxx = shutil.which("g++")
     if gxx is None:
         pytest.skip("no g++ on this machine")
@@ -34,12 +42,18 @@ def driver(tmp_path_factory):
                     os.path.join(HERE, "rollup_plan_driver.cpp"), "-o", exe],
                    check=True)
 
-    def run(aggs, eps, every=1024):
-        r = subprocess.run([exe, repr(eps), str(every)] +
-                           [str(AGG[a]) for a in aggs],
+    def run(*args):
+        r = subprocess.run([exe] + [str(a) for a in args],
                            capture_output=True, text=True)
         assert r.returncode == 0, r.stderr
         return json.loads(r.stdout)
+    return run
+
+
+@pytest.fixture(scope="module")
+def driver(driver_exe):
+    def run(aggs, eps, every=1024):
+        return driver_exe(repr(eps), every, *[AGG[a] for a in aggs])
     return run
 
 
@@ -128,3 +142,83 @@ def test_plan_unsorted_full_width(driver):
         got = driver(aggs, eps)
         assert got["nq"] == 15
         assert got == plan_py(aggs, eps)
+
+
+# ---------------- the exact-quantile index the kernels share ----------------
+
+def quantile_index_py(qs, qi, n):
+    """Same rule as all_resolve_to_max, as an index into the sorted values."""
+    if n <= 3:
+        return min(int(qs[qi] * n), n - 1)
+    k = 0
+    for i, q in enumerate(qs[:qi + 1]):
+        k = math.ceil(q * n) if i == 0 else max(math.ceil(q * n), k + 1)
+    return min(k, n) - 1
+
+
+FULL_WIDTH = ["p9999", "p999", "p99", "p95", "p90", "p80", "p75", "p70", "p60",
+              "median", "p50", "p40", "p30", "p25", "p20", "p10"]
+
+
+@pytest.mark.parametrize("qset", [t[0] for t in TABLE] +
+                         [["median", "p50", "p95"], FULL_WIDTH],
+                         ids=lambda q: "+".join(q[:4]))
+def test_quantile_index(driver_exe, qset):
+    qs = sorted({QUANTILE[a] for a in qset})
+    got = driver_exe("qindex", repr(1e-3), 1024, *[AGG[a] for a in qset])
+    assert len(got) == QCAP
+    for n in range(1, QCAP + 1):
+        want = [quantile_index_py(qs, qi, n) for qi in range(len(qs))]
+        assert got[n - 1] == want, n
+        assert all(0 <= i < n for i in want)
+        # extreme_cap is this index being n-1 for every quantile
+        assert all_resolve_to_max(qs, n) == all(i == n - 1 for i in want)
+
+
+# ------------- bucket accumulate + ValueOf against the oracle -------------
+
+T0 = 1427162400 * 10**9
+WINDOW = 60 * 10**9
+NAN = float("nan")
+ALL_AGGS = ["last", "min", "max", "mean", "count", "sum", "sumsq", "stdev"]
+# metric -> (id, aggs whose ValueOf reads the bucket state alone)
+METRICS = {
+    "counter": (oracle.METRIC_COUNTER, ALL_AGGS),
+    "gauge": (oracle.METRIC_GAUGE, ALL_AGGS),
+    "timer": (oracle.METRIC_TIMER, ["mean", "count", "sum", "sumsq", "stdev"]),
+}
+S = 10**9
+BUCKETS = {   # name -> [(seconds into the window, value)], int64-safe values
+    "empty": [],
+    "one": [(3, 42.0)],
+    "several": [(0, 1.5), (10, 2.5), (20, -7.25), (59, 1e6)],
+    "negative": [(0, -5.0), (1, -300.0), (2, 17.0), (3, -2.0**31)],
+    "fractions_truncate": [(0, 2.9), (1, -2.9), (2, 0.5)],
+    "large": [(0, 2.0**30), (1, -2.0**30), (2, 2.0**31 - 1)],
+    "nan_between": [(0, 1.0), (1, NAN), (2, -3.0), (3, NAN)],
+    "nan_first": [(0, NAN), (1, 4.0)],
+    "all_nan": [(0, NAN), (1, NAN)],
+    "equal_ts": [(5, 1.0), (5, 2.0), (5, 3.0)],
+}
+# a counter casts NaN to INT64_MIN, whose square leaves the int64 range
+CASES = [(m, b) for m in METRICS for b in BUCKETS
+         if not (m == "counter" and "nan" in b)]
+
+
+@pytest.mark.parametrize("metric,bucket", CASES)
+def test_bucket_value_of_matches_oracle(driver_exe, metric, bucket):
+    mid, aggs = METRICS[metric]
+    pts = BUCKETS[bucket]
+    # the bucket under test is bucket 1 of 3, between two one-point buckets,
+    # so that the oracle emits it when it is empty as well
+    ts = [T0 + 1 * S] + [T0 + WINDOW + s * S for s, _ in pts] + [T0 + 2 * WINDOW]
+    vals = [1.0] + [v for _, v in pts] + [1.0]
+    o_out, _ = oracle.rollup_batch(np.array([ts]), np.array([vals]),
+                                   np.array([len(ts)], np.uint32), mid, WINDOW,
+                                   3, aggs)
+    args = []
+    for s, v in pts:
+        args += [T0 + WINDOW + s * S, repr(v)]
+    got = driver_exe("bucket", mid, len(aggs), *[AGG[a] for a in aggs], *args)
+    want = [int(b) for b in o_out[0, 1].view(np.uint64)]
+    assert got == want, dict(zip(aggs, zip(got, want)))
