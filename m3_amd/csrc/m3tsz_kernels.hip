@@ -977,6 +977,19 @@ using RingDecoder = DecoderT<true>;  /* series-per-lane kernels: LDS ring */
 #ifndef RF_SPAN
 #define RF_SPAN 2
 #endif
+/* k_decode_batch only: the span of a tile whose predecessor left every
+ * lane's ring with words to spare (see its tile loop). DEC_TILE = one burst
+ * per tile; RF_SPAN = the fixed span everywhere. A tile counts as calm
+ * after one in which no lane pulled more than RF_CALM_MAX words. Same box,
+ * the fixed span alone, one stream kind at a time: one-decimal
+ * gauges (1-2 words a tile) 11.1 ms at span 2, 10.0 at 8; counters (2-3
+ * words a tile, dry about every other tile at span 8) 11.75 and 11.91. */
+#ifndef RF_SPAN_CALM
+#define RF_SPAN_CALM DEC_TILE
+#endif
+#ifndef RF_CALM_MAX
+#define RF_CALM_MAX (IN_WORDS - 1)
+#endif
 
 /* Cache policy of the flush's output stores: 0 plain, 1 non-temporal (nt),
  * 2 write-through (sc1). Plain and nt stores keep their line in the XCD's
@@ -1228,26 +1241,43 @@ k_decode_batch(const uint8_t* __restrict__ blobs,
         }
     };
 
+    /* The top-up span is a per-wave, per-tile choice. A calm tile runs at
+     * RF_SPAN_CALM = DEC_TILE: one burst right after the previous tile's
+     * flush, one commit right before this tile's, and between them the
+     * wave touches VALU and LDS only — it cannot queue behind another
+     * wave's output stores. A tile is calm when in the tile before it no
+     * running lane pulled more than IN_WORDS - 1 words and none ran its
+     * ring dry (wnext beyond rfill at a commit: the in-chain load, or the
+     * zero words past the stream's end). The first tile, and every tile
+     * after a busy one, runs at RF_SPAN. Only the schedule of the loads
+     * depends on this: what a lane reads and decodes does not. */
+    uint32_t span = RF_SPAN;
     while (__any(running)) {
         /* wave-uniform capacity flag: cnt <= k + j, so the per-point
          * check matters only on a tile that could cross `stride` */
         const bool check_cap = k + DEC_TILE > stride;
+        const uint32_t w0 = d.r.wnext;
+        bool dry = false;
         /* NOT unrolled, neither loop: the fully-inlined parser is ~10k
          * instructions — it is instantiated exactly once */
 #pragma unroll 1
-        for (uint32_t h = 0; h < DEC_TILE; h += RF_SPAN) {
+        for (uint32_t h = 0; h < DEC_TILE; h += span) {
             /* scoped to one top-up span: the registers are written by the
              * loads here and first read by the commit below, nothing in
              * between */
             const RingPending pd = d.r.refill_issue(running);
 #pragma unroll 1
-            for (uint32_t j = h; j < h + RF_SPAN; j++) step(j, check_cap);
+            for (uint32_t j = h; j < h + span; j++) step(j, check_cap);
+            dry |= d.r.wnext > d.r.rfill;
             /* the last commit comes BEFORE the flush: its vmcnt wait then
              * covers only this span's loads plus the PREVIOUS tile's
              * stores (issued a tile ago, long retired) — never the 16
              * stores the flush is about to issue */
             d.r.refill_commit(pd);
         }
+        span = __all(!running ||
+                     (!dry && d.r.wnext - w0 <= RF_CALM_MAX))
+                   ? RF_SPAN_CALM : RF_SPAN;
         flush(k);
         if constexpr (FULL) {
             flush_units(k);
