@@ -37,6 +37,7 @@
 #include <atomic>
 #include <math.h>
 #include <string.h>
+#include <type_traits>
 #include <stdio.h>
 #include "../../include/m3gpu.h"
 #include "rollup_plan.h" /* QCAP, MAX_AGGS, m3::RollupPlan + its host builder */
@@ -116,16 +117,13 @@ __device__ __forceinline__ double go_modf(double v, double* ip) {
 /* istream.go:73-115 over reader64.go:40-80, with the m3gpu.h layout
  * contract: stream starts 8B-aligned, buffer zero-padded to 8B. */
 
-/* Per-lane LDS input ring geometry (series-per-lane kernels): IN_WORDS
- * buffered u64 words per lane, rows IN_STRIDE words apart (unpadded: 4
- * words x 64 lanes x 4 waves = 8 KB/block, which together with the 32 KB
- * output tile keeps 4 blocks/CU; an 8-word ring drops that to 3 and
- * measured slower). IN_WORDS must be a power of two. */
+/* Per-lane LDS input ring (series-per-lane kernels), rows [wave][lane][depth].
+ * The depth (buffered u64 words per lane, a power of two) is a template
+ * parameter of the reader, so each kernel picks its own:
+ *  - IN_WORDS = 4 (8 KB/block): k_rollup_lane and k_step_fused.
+ *  - DEC_RING = 8 (16 KB/block): k_decode_batch, see there. */
 #ifndef IN_WORDS
 #define IN_WORDS 4
-#endif
-#ifndef IN_STRIDE
-#define IN_STRIDE 4
 #endif
 
 /* The ring pointer carries its address space in its type: a generic pointer
@@ -138,16 +136,38 @@ typedef __attribute__((address_space(3))) uint64_t lds_u64;
  * in the tile loop's scope, NOT in the reader: nothing may read, copy or
  * select these registers between refill_issue() and refill_commit(), or
  * the compiler has to wait for the loads (vmcnt) right there. */
-struct RingPending {
-    uint64_t w[IN_WORDS];
+template <int DEPTH>
+struct RingPendingT {
+    uint64_t w[DEPTH];
     uint32_t n;
 };
+using RingPending = RingPendingT<IN_WORDS>;
 
-/* RING is a compile-time property of the kernel: true for the
- * series-per-lane kernels (k_decode_batch, k_rollup_lane), false for the
- * wave-per-series rollup and CKMS kernels. */
-template <bool RING>
+/* The same for the 16-byte refill (BitReader WIDE): a burst of n words from
+ * `src` is a leading single word where src is not 16-byte aligned, then
+ * 16-byte pairs, then a trailing single word where an odd number is left.
+ * Every register is written by at most one load. */
+typedef unsigned long long ring_u64x2 __attribute__((ext_vector_type(2)));
+template <int DEPTH>
+struct RingPendingWideT {
+    uint64_t head, tail;
+    ring_u64x2 pr[DEPTH / 2];
+    uint32_t n, odd;
+};
+
+/* RING is a compile-time property of the kernel: the ring's depth in words
+ * for the series-per-lane kernels (k_decode_batch, k_rollup_lane,
+ * k_step_fused), 0 for the wave-per-series rollup and CKMS kernels (direct
+ * reader); the ring is the lane's own row of RING consecutive words. WIDE
+ * picks the 16-byte form of the top-up's loads (k_decode_batch). */
+template <int RING, bool WIDE = false>
 struct BitReader {
+    static_assert(RING >= 0 && (RING & (RING - 1)) == 0,
+                  "ring depth: 0 (direct) or a power of two");
+    static_assert(!WIDE || RING >= 2, "16-byte refill: ring mode only");
+    using Pending = typename std::conditional<
+        WIDE, RingPendingWideT<RING ? RING : 2>,
+        RingPendingT<RING ? RING : 1>>::type;
     /* 128-bit register lookahead (`a` = next bits, `b` = following word,
      * both byte-swapped to stream bit order; `p` = bits of `a` already
      * consumed): peek64() is branch-free, consume() crosses at most one
@@ -159,7 +179,7 @@ struct BitReader {
      *
      * Words arrive one of two ways:
      *  - ring (RING): refill_issue()/refill_commit() top the per-lane
-     *    IN_WORDS-word LDS ring up once per 8-point tile with consecutive
+     *    RING-word LDS ring up once per 8-point tile with consecutive
      *    words of the lane's own stream, so the long-latency global
      *    gathers leave the per-point dependency chain: the parser's word
      *    pulls are ds_read_b64s. A lane that drains its ring inside a
@@ -181,12 +201,12 @@ struct BitReader {
 
     __device__ __forceinline__ uint64_t next_word() {
         uint64_t w;
-        if constexpr (RING) {
+        if constexpr (RING != 0) {
             /* ring hit is the steady state (refill runs per tile); a
              * mid-tile underrun (streams consuming more than the ring
              * holds in 8 points) falls back to a direct load — correct,
              * just slower, and its wait drains every store in flight */
-            if (wnext < rfill) w = lds[wnext & (IN_WORDS - 1)];
+            if (wnext < rfill) w = lds[wnext & (RING - 1)];
             else w = (wnext < wtotal) ? __builtin_bswap64(words[wnext]) : 0;
         } else {
             w = pfw;
@@ -198,7 +218,7 @@ struct BitReader {
     }
 
     /* Deferred ring top-up. refill_issue() runs at the start of a span of
-     * points with the whole wave converged and issues up to IN_WORDS global
+     * points with the whole wave converged and issues up to RING global
      * loads per lane back to back; refill_commit() byte-swaps them and
      * writes them to the ring at the end of the span, before the tile's
      * output stores issue. gfx9 vmcnt retires in issue order, so the
@@ -215,52 +235,104 @@ struct BitReader {
      * or select at the branch's join, nothing touches the register until
      * the commit, and the compiler places no wait at the issue. */
 #ifndef RF_LOW
-#define RF_LOW 3 /* refill when <= this many ring words remain. Topping up
+#define RF_LOW 3 /* 4-word ring: refill when <= this many words remain (that
+                  * is always; the 8-word ring of k_decode_batch has its
+                  * own DEC_RF_LOW). Topping up
                   * word by word at every chance re-fetches each 64B line
                   * several times (FETCH_SIZE ~5x the stream) but keeps the
                   * ring from drying inside a span; whole-ring-only refills
                   * (RF_LOW 0) were re-measured with the deferred refill in
                   * place and still lose: 16.57 vs 16.11 ms */
 #endif
-    __device__ __forceinline__ RingPending refill_issue(bool active) {
-        static_assert(RING, "ring mode only");
+    template <uint32_t LOW = RF_LOW>
+    __device__ __forceinline__ Pending refill_issue(bool active) {
+        static_assert(RING != 0, "ring mode only");
         if (rfill < wnext) rfill = wnext; /* resync: underrun consumed
                                            * [rfill, wnext) directly */
         const uint32_t used = rfill - wnext;
         uint32_t n = wtotal - rfill;
-        const uint32_t room = IN_WORDS - used;
+        const uint32_t room = RING - used;
         if (n > room) n = room;
-        if (!(active && used <= RF_LOW && rfill < wtotal)) n = 0;
-        RingPending pd;
+        if (!(active && used <= LOW && rfill < wtotal)) n = 0;
+        Pending pd;
         pd.n = n;
+        if constexpr (WIDE) {
+            /* words [odd, odd + 2 * npair) of the burst go as 16-byte
+             * loads from 16-byte aligned addresses, never past word n - 1
+             * (the word behind a stream's last is another stream's, or
+             * none); the one in front and the one behind as 8-byte loads */
+            const uint64_t* src = words + rfill;
+            const uint32_t odd = (uint32_t)((uintptr_t)src >> 3) & 1;
+            pd.odd = odd;
+            pd.head = 0;
+            if (odd && n > 0) pd.head = src[0];
 #pragma unroll
-        for (uint32_t i = 0; i < IN_WORDS; i++) {
-            pd.w[i] = 0;
-            if (i < n) pd.w[i] = words[rfill + i];
+            for (uint32_t j = 0; j < RING / 2; j++) {
+                pd.pr[j] = ring_u64x2{0, 0};
+                if (odd + 2 * j + 1 < n)
+                    pd.pr[j] = *(const ring_u64x2*)(src + odd + 2 * j);
+            }
+            pd.tail = 0;
+            if (n > odd && ((n - odd) & 1)) pd.tail = src[n - 1];
+        } else {
+#pragma unroll
+            for (uint32_t i = 0; i < RING; i++) {
+                pd.w[i] = 0;
+                if (i < n) pd.w[i] = words[rfill + i];
+            }
         }
         return pd;
     }
-    __device__ __forceinline__ void refill_commit(const RingPending& pd) {
-        static_assert(RING, "ring mode only");
+    __device__ __forceinline__ void refill_commit(const Pending& pd) {
+        static_assert(RING != 0, "ring mode only");
         /* The one place the burst is waited for, by the whole wave and for
-         * all IN_WORDS loads at once. The empty asm only pins that: it
+         * all RING loads at once. The empty asm only pins that: it
          * "uses" each raw word here, so (a) the compiler cannot fold the
          * byte swap below back up into refill_issue() (it would wait for
          * the loads right where they issue), and (b) no load is left
          * pending past the commit when no lane wanted its word — the next
          * tile's burst would then have to wait for it behind this tile's
          * output stores. */
-        uint64_t w[IN_WORDS];
+        if constexpr (WIDE) {
+            uint64_t head = pd.head, tail = pd.tail;
+            uint64_t w[RING];
+            asm volatile("" : "+v"(head));
 #pragma unroll
-        for (uint32_t i = 0; i < IN_WORDS; i++) {
-            w[i] = pd.w[i];
-            asm volatile("" : "+v"(w[i]));
+            for (uint32_t j = 0; j < RING / 2; j++) {
+                ring_u64x2 v = pd.pr[j];
+                asm volatile("" : "+v"(v));
+                w[2 * j] = v.x;
+                w[2 * j + 1] = v.y;
+            }
+            asm volatile("" : "+v"(tail));
+            const uint32_t n = pd.n, odd = pd.odd;
+            if (odd && n > 0)
+                lds[rfill & (RING - 1)] = __builtin_bswap64(head);
+#pragma unroll
+            for (uint32_t j = 0; j < RING / 2; j++)
+                if (odd + 2 * j + 1 < n) {
+                    lds[(rfill + odd + 2 * j) & (RING - 1)] =
+                        __builtin_bswap64(w[2 * j]);
+                    lds[(rfill + odd + 2 * j + 1) & (RING - 1)] =
+                        __builtin_bswap64(w[2 * j + 1]);
+                }
+            if (n > odd && ((n - odd) & 1))
+                lds[(rfill + n - 1) & (RING - 1)] =
+                    __builtin_bswap64(tail);
+            rfill += n;
+        } else {
+            uint64_t w[RING];
+#pragma unroll
+            for (uint32_t i = 0; i < RING; i++) {
+                w[i] = pd.w[i];
+                asm volatile("" : "+v"(w[i]));
+            }
+#pragma unroll
+            for (uint32_t i = 0; i < RING; i++)
+                if (i < pd.n)
+                    lds[(rfill + i) & (RING - 1)] = __builtin_bswap64(w[i]);
+            rfill += pd.n;
         }
-#pragma unroll
-        for (uint32_t i = 0; i < IN_WORDS; i++)
-            if (i < pd.n)
-                lds[(rfill + i) & (IN_WORDS - 1)] = __builtin_bswap64(w[i]);
-        rfill += pd.n;
     }
 
     __device__ __forceinline__ void init(const uint8_t* base, uint64_t off,
@@ -269,11 +341,11 @@ struct BitReader {
         wtotal = (l + 7) >> 3;
         bits_left = (int64_t)l * 8;
         wnext = 0;
-        if constexpr (RING) {
+        if constexpr (RING != 0) {
             lds = (lds_u64*)ring;
             rfill = 0;
             /* called with the whole wave converged */
-            const RingPending pd = refill_issue(true);
+            const Pending pd = refill_issue(true);
             refill_commit(pd);
         } else {
             pfw = wtotal ? __builtin_bswap64(words[0]) : 0;
@@ -316,9 +388,9 @@ struct BitReader {
 /* Port of the reference decode state machine: iterator.go:47-219,
  * timestamp_iterator.go:41-361, float_encoder_iterator.go:105-165. */
 
-template <bool RING>
+template <int RING, bool WIDE = false>
 struct DecoderT {
-    BitReader<RING> r;
+    BitReader<RING, WIDE> r;
     int64_t prev_time, prev_time_delta;
     int64_t unit_ns; /* cached UNIT_NS_D[time_unit] (0 when unit invalid) */
     double mult_pow;  /* cached 10^mult (mult changes rarely; keeping the
@@ -340,7 +412,7 @@ struct DecoderT {
          * unit_ns, which is in the per-point path, and the vmcnt(0) there
          * drains the ring top-up and every output store in flight. */
         int64_t ns = unit_valid(tu) ? UNIT_NS_D[tu] : 0;
-        if constexpr (RING) asm volatile("" : "+v"(ns));
+        if constexpr (RING != 0) asm volatile("" : "+v"(ns));
         unit_ns = ns;
     }
 
@@ -936,8 +1008,8 @@ struct DecoderT {
     }
 };
 
-using Decoder = DecoderT<false>;     /* wave-per-series kernels: direct reader */
-using RingDecoder = DecoderT<true>;  /* series-per-lane kernels: LDS ring */
+using Decoder = DecoderT<0>;             /* wave-per-series kernels: direct reader */
+using RingDecoder = DecoderT<IN_WORDS>;  /* series-per-lane kernels: 4-word LDS ring */
 
 /* ========================= decode kernel ========================= */
 /* ONE SERIES PER LANE: a wave decodes 64 independent streams in parallel,
@@ -949,7 +1021,7 @@ using RingDecoder = DecoderT<true>;  /* series-per-lane kernels: LDS ring */
  * Memory structure:
  *  - INPUT through a per-lane LDS ring (BitReader::refill_issue/_commit):
  *    the global gathers leave the per-point chain — every RF_SPAN points
- *    each lane issues up to IN_WORDS loads of consecutive words of its own
+ *    each lane loads up to DEC_RING consecutive words of its own
  *    stream, commits them to its ring RF_SPAN points later, and the parser
  *    pulls words with ds_read_b64s.
  *  - OUTPUT staged in an LDS tile, [64 lanes][8 points] of (ts, val) pairs
@@ -963,9 +1035,42 @@ using RingDecoder = DecoderT<true>;  /* series-per-lane kernels: LDS ring */
  *    is made once per launch. OUT_POLICY picks the stores' cache policy. */
 
 #define DEC_TILE 8
+/* k_decode_batch's input ring: 8 words per lane. The dense stream kinds
+ * pull 6-8 words per 8-point tile and counters 2-3: a 4-word ring runs dry
+ * inside a tile for the former and about every other calm tile for the
+ * latter, and every dry-out is an in-chain load whose vmcnt(0) drains the
+ * output stores in flight. 8 words x 64 lanes x 4 waves = 16 KB, with the
+ * 32 KB output tile 48 KB/block: 3 blocks/CU, 3 waves/SIMD, and a VGPR
+ * budget of 168 instead of 128. Same box, three alternated runs each
+ * (DESIGN.md §4): 13.95 / 13.93 / 13.90 ms at 4 words, 12.94 / 12.91 /
+ * 11.90 at 8.
+ * The ring is lane-major, [wave][lane][8]: rows of 64 bytes put the 32
+ * lanes of a ds_read_b64 group on 4 bank pairs, and a word-major ring
+ * [wave][8][lane] is conflict-free (SQ_LDS_BANK_CONFLICT 93.5M -> 0 per
+ * 250k-series launch, SQ_LDS_IDX_ACTIVE 226M -> 131M) — and 0.6% SLOWER,
+ * 11.29 / 11.30 / 11.31 ms against 11.23 / 11.23 / 11.23: the LDS is not
+ * what the kernel waits for. */
+#ifndef DEC_RING
+#define DEC_RING 8
+#endif
+/* 1: a burst loads 16 bytes per lane and instruction where the address
+ * allows (BitReader WIDE); 0: 8 bytes always. A per-lane load costs its
+ * line requests whatever its width, so the wide form about halves the
+ * burst's requests: same box, three alternated runs each, 11.40 / 11.36 /
+ * 11.34 ms narrow against 10.91 / 10.91 / 10.91 wide, `--data production`
+ * 4.27 / 4.21 / 4.17 against 4.12 / 4.12 / 3.97. */
+#ifndef DEC_REFILL_WIDE
+#define DEC_REFILL_WIDE 1
+#endif
+/* top the 8-word ring up when <= this many words remain. Same box, three
+ * alternated runs each: 2 13.02 ms, 3 11.34-11.40, 5 11.47, 7 12.45-13.44
+ * against 11.91-12.90 for 3 in that call. */
+#ifndef DEC_RF_LOW
+#define DEC_RF_LOW 3
+#endif
 /* points parsed between a ring top-up's issue and its commit; divides
- * DEC_TILE. 2 = four top-ups per tile: the dense stream kinds consume 6-8
- * words per 8 points, twice what the ring holds, and with one top-up per
+ * DEC_TILE. 2 = four top-ups per tile (figures from the 4-word ring): the
+ * dense stream kinds consume 6-8 words per 8 points, and with one top-up per
  * tile they spend half of every tile in the parser's in-chain underrun
  * load, whose vmcnt(0) also drains the output stores. The span trades that
  * against how long a load has to land before its commit waits for it.
@@ -988,7 +1093,7 @@ using RingDecoder = DecoderT<true>;  /* series-per-lane kernels: LDS ring */
 #define RF_SPAN_CALM DEC_TILE
 #endif
 #ifndef RF_CALM_MAX
-#define RF_CALM_MAX (IN_WORDS - 1)
+#define RF_CALM_MAX (DEC_RING - 1)
 #endif
 
 /* Cache policy of the flush's output stores: 0 plain, 1 non-temporal (nt),
@@ -1074,12 +1179,12 @@ struct DecodeFullOut {
 
 /* FULL = false is the bulk kernel; `full` is not touched. FULL = true also
  * returns ReaderIterator.Current()'s unit for every stored point and the
- * stream's first 64 bits. The units take no LDS (the 40 KB of ring + tile
- * already fill a CU's 160 KB four times): a lane packs its own 8 unit bytes
+ * stream's first 64 bits. The units take no LDS (the 48 KB of ring + tile
+ * already fill a CU's 160 KB three times): a lane packs its own 8 unit bytes
  * of the tile into one 64-bit register and stores its own row at the flush. */
 template <bool FULL>
-__global__ void __launch_bounds__(BLOCK_THREADS, 4) /* hold the 128-VGPR
-    granule: ring + tiles = 40 KB/block -> 4 blocks/CU, 4 waves/SIMD */
+__global__ void __launch_bounds__(BLOCK_THREADS, 3) /* ring + tiles = 48
+    KB/block -> 3 blocks/CU, 3 waves/SIMD: a 168-VGPR budget */
 k_decode_batch(const uint8_t* __restrict__ blobs,
                const uint64_t* __restrict__ offsets,
                const uint32_t* __restrict__ lens,
@@ -1101,13 +1206,13 @@ k_decode_batch(const uint8_t* __restrict__ blobs,
     /* input ring + output tile. The tile is AoS — (ts, val) PAIRS, one
      * ds_write_b128 per point instead of two b64s — with a pair-granular
      * XOR column swizzle (col ^ (lane & 7)). */
-    __shared__ uint64_t ring_all[WAVES_PER_BLOCK][WAVE][IN_STRIDE];
+    __shared__ uint64_t ring_all[WAVES_PER_BLOCK][WAVE][DEC_RING];
     __shared__ longlong2 tile_all[WAVES_PER_BLOCK][WAVE][DEC_TILE];
     uint64_t* ring = ring_all[wave][lane];
     longlong2 (*tile)[DEC_TILE] = tile_all[wave];
 
     const bool in_range = slot < nseries;
-    RingDecoder d;
+    DecoderT<DEC_RING, DEC_REFILL_WIDE != 0> d;
     d.init(blobs, in_range ? offsets[series] : 0, in_range ? lens[series] : 0,
            int_optimized != 0, default_unit, ring,
            (out_ann && in_range) ? out_ann + (uint64_t)series * ann_stride
@@ -1246,7 +1351,7 @@ k_decode_batch(const uint8_t* __restrict__ blobs,
      * flush, one commit right before this tile's, and between them the
      * wave touches VALU and LDS only — it cannot queue behind another
      * wave's output stores. A tile is calm when in the tile before it no
-     * running lane pulled more than IN_WORDS - 1 words and none ran its
+     * running lane pulled more than RF_CALM_MAX words and none ran its
      * ring dry (wnext beyond rfill at a commit: the in-chain load, or the
      * zero words past the stream's end). The first tile, and every tile
      * after a busy one, runs at RF_SPAN. Only the schedule of the loads
@@ -1265,7 +1370,7 @@ k_decode_batch(const uint8_t* __restrict__ blobs,
             /* scoped to one top-up span: the registers are written by the
              * loads here and first read by the commit below, nothing in
              * between */
-            const RingPending pd = d.r.refill_issue(running);
+            const auto pd = d.r.template refill_issue<DEC_RF_LOW>(running);
 #pragma unroll 1
             for (uint32_t j = h; j < h + span; j++) step(j, check_cap);
             dry |= d.r.wnext > d.r.rfill;
@@ -2867,7 +2972,7 @@ k_step_fused(const uint8_t* __restrict__ blobs,
     const uint32_t series = blockIdx.x * BLOCK_THREADS + threadIdx.x;
     const bool in_range = series < nseries;
 
-    __shared__ uint64_t ring_all[WAVES_PER_BLOCK][WAVE][IN_STRIDE];
+    __shared__ uint64_t ring_all[WAVES_PER_BLOCK][WAVE][IN_WORDS];
     __shared__ uint64_t tile_all[WAVES_PER_BLOCK][STEP_TILE][WAVE];
     uint64_t* ring = ring_all[wave][lane];
     uint64_t* col = &tile_all[wave][0][lane];

@@ -160,7 +160,7 @@ k_rollup_lane(const uint8_t* __restrict__ blobs,
                               [WITH_Q ? WAVE : 1][WITH_Q ? RQCAP_LANE : 1];
     double* qrow = WITH_Q ? qbuf_all[wave][lane] : nullptr;
     /* per-lane input ring, as in k_decode_batch */
-    __shared__ uint64_t rring_all[WAVES_PER_BLOCK][WAVE][IN_STRIDE];
+    __shared__ uint64_t rring_all[WAVES_PER_BLOCK][WAVE][IN_WORDS];
     uint64_t* rring = rring_all[wave][lane];
 
     const bool in_range = series < nseries;
