@@ -3430,7 +3430,7 @@ int m3gpu_rollup_batch_dev_opts(
 
     /* One retry tier: rerun the series still flagged as overflowed on the
      * wave-per-series kernel, or (ckms) on the real compressed CKMS
-     * (k_rollup_ckms, one series per workgroup, ~145 KB dynamic LDS), and
+     * (k_rollup_ckms, one series per workgroup, ~129 KB dynamic LDS), and
      * wait for it, since the next step reads the flags it rewrites. */
     auto run_tier = [&](bool ckms) -> int {
         DevBuf<int32_t> sel;

@@ -27,6 +27,19 @@ M3_HD static M3_INLINE int64_t go_f2i(double v) {
     return (int64_t)v;
 }
 
+/* The timer values whose place in the reference's CKMS stream depends on
+ * more than their order among the bucket's values: a NaN fails both insert
+ * compares and is dropped with what the heap sort left behind it
+ * (stream.go:305,325), and a zero with the sign bit set ties with +0.0,
+ * where the heaps decide which comes first (heap.go:36-54,92-121). Only
+ * the ckms tier restates that; the exact tiers hand such a bucket on. */
+M3_HD static M3_INLINE bool timer_value_needs_stream(double v) {
+    uint64_t u;
+    __builtin_memcpy(&u, &v, sizeof(u));
+    return u == 0x8000000000000000ull ||
+           (u & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull;
+}
+
 /* ---- the bucket walk ---- */
 #define WALK_SAME 0      /* the point belongs to the open bucket */
 #define WALK_ADVANCE (-1) /* see BucketWalk::step */

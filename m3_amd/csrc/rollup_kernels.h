@@ -21,6 +21,9 @@
  *
  * A tier that cannot hold a bucket flags M3GPU_SERIES_BUCKET_OVERFLOW and
  * writes nothing more for that series: the host reruns it on the next tier.
+ * The three exact timer-quantile tiers (staged, extreme, wave) do the same
+ * on a NaN or a -0.0 (timer_value_needs_stream): where those end up in the
+ * reference's stream depends on its heaps, which only the ckms tier keeps.
  */
 #ifndef M3_ROLLUP_KERNELS_H
 #define M3_ROLLUP_KERNELS_H
@@ -120,7 +123,9 @@ k_rollup_batch(const uint8_t* __restrict__ blobs,
             bs.reset();
             n = 0;
         }
-        if (n >= (uint32_t)plan.exact_cap || n >= QCAP) {
+        /* a NaN or a -0.0 needs the stream itself: the ckms tier */
+        if (n >= (uint32_t)plan.exact_cap || n >= QCAP ||
+            timer_value_needs_stream(v)) {
             err = M3GPU_SERIES_BUCKET_OVERFLOW;
             break;
         }
@@ -258,13 +263,16 @@ k_rollup_lane(const uint8_t* __restrict__ blobs,
                 }
                 if (ok) {
                     if (QMODE == RQ_EXTREME &&
-                        (isnan(v) || bs.count >= (int64_t)plan.extreme_cap)) {
-                        /* NaN ordering and deep buckets keep the exact
-                         * staged semantics: retry on the wave tier */
+                        (timer_value_needs_stream(v) ||
+                         bs.count >= (int64_t)plan.extreme_cap)) {
+                        /* deep buckets keep the exact staged semantics on
+                         * the wave tier; a NaN or a -0.0 passes through it
+                         * to the ckms tier */
                         err = M3GPU_SERIES_BUCKET_OVERFLOW;
                         running = false;
                     } else if (WITH_Q && (nq >= RQCAP_LANE ||
-                                          nq >= (uint32_t)plan.exact_cap)) {
+                                          nq >= (uint32_t)plan.exact_cap ||
+                                          timer_value_needs_stream(v))) {
                         err = M3GPU_SERIES_BUCKET_OVERFLOW;
                         running = false;
                     } else {
@@ -330,8 +338,13 @@ k_count_errcode(const int32_t* __restrict__ errs, uint32_t n, int32_t code,
  *  - in the AddBatch(1)/Flush usage the compress cursor is always nil on
  *    insert entry, so the compValue/compressMinRank-in-insert branch of the
  *    reference is dead (stream.go:284-287,303) and omitted;
- *  - buffers bufLess/bufMore are value MULTISETS here (the reference's heap
- *    order only permutes ties, which insert() cannot distinguish);
+ *  - buffers bufLess/bufMore are the reference's min-heaps (heap.go:36-54
+ *    Push, :92-121 SortDesc), kept by lane 0: the heap order decides where
+ *    a -0.0 lands among +0.0 and what a NaN takes with it when insert()
+ *    drops it, and both show in the output bits;
+ *  - insert() keeps the reference's compares (<= the cursor, >= the tail):
+ *    a value that fails both is dropped with the rest of the sorted
+ *    buffer, and numValues grows by what was inserted;
  *  - capacity overflow (sample list or buffer > CKMS_CAP) flags
  *    M3GPU_SERIES_BUCKET_OVERFLOW — never an approximation. */
 #define CKMS_CAP 3072
@@ -347,8 +360,7 @@ struct CkmsLdsLayout {
     static constexpr uint32_t dl = nr + 2 * CKMS_CAP * 4;     /* int32_t[2][CKMS_CAP] */
     static constexpr uint32_t less = dl + 2 * CKMS_CAP * 4;   /* double[CKMS_BUF] */
     static constexpr uint32_t more = less + CKMS_BUF * 8;     /* double[CKMS_BUF] */
-    static constexpr uint32_t sorted = more + CKMS_BUF * 8;   /* double[CKMS_BUF] */
-    static constexpr uint32_t computed = sorted + CKMS_BUF * 8;      /* double[MAX_AGGS] */
+    static constexpr uint32_t computed = more + CKMS_BUF * 8;        /* double[MAX_AGGS] */
     static constexpr uint32_t thr_rank = computed + MAX_AGGS * 8;    /* int64_t[MAX_AGGS] */
     static constexpr uint32_t thr_thresh = thr_rank + MAX_AGGS * 8;  /* int64_t[MAX_AGGS] */
     static constexpr uint32_t bytes = thr_thresh + MAX_AGGS * 8;
@@ -380,22 +392,40 @@ __device__ __forceinline__ void ckms_reset(CkmsState& st) {
     st.counter = 0;
 }
 
-/* wave-parallel ascending sort of buf[0..n) into tmp[0..n) (rank-select) */
-__device__ __forceinline__ void ckms_sort(const double* buf, double* tmp,
-                                          int32_t n, uint32_t lane) {
-    __builtin_amdgcn_wave_barrier();
-    __threadfence_block();
-    for (int32_t e = lane; e < n; e += WAVE) {
-        double v = buf[e];
-        int32_t rank = 0;
-        for (int32_t j = 0; j < n; j++) {
-            double o = buf[j];
-            rank += (o < v) || (o == v && j < e);
-        }
-        tmp[rank] = v;
+/* heap.go:36-54 Push onto heap[0..n): the new value sifts up while its
+ * parent is not <= it (a NaN therefore climbs to the root). Lane 0 only. */
+__device__ __forceinline__ void ckms_heap_push(double* heap, int32_t n, double v) {
+    int32_t i = n;
+    heap[i] = v;
+    while (i > 0) {
+        int32_t parent = (i - 1) / 2;
+        double p = heap[parent];
+        if (p <= v) break;
+        heap[parent] = v;
+        heap[i] = p;
+        i = parent;
     }
-    __builtin_amdgcn_wave_barrier();
-    __threadfence_block();
+}
+
+/* heap.go:92-121 SortDesc: pop the minimum to the end, n-1 times, with the
+ * reference's strict < in the sift-down. Lane 0 only. */
+__device__ void ckms_heap_sort_desc(double* heap, int32_t len) {
+    for (int32_t n = len - 1; n > 0; n--) {
+        double t = heap[0];
+        heap[0] = heap[n];
+        heap[n] = t;
+        int32_t i = 0;
+        for (;;) {
+            int32_t smallest = i, left = 2 * i + 1, right = left + 1;
+            if (left < n && heap[left] < heap[smallest]) smallest = left;
+            if (right < n && heap[right] < heap[smallest]) smallest = right;
+            if (smallest == i) break;
+            t = heap[i];
+            heap[i] = heap[smallest];
+            heap[smallest] = t;
+            i = smallest;
+        }
+    }
 }
 
 /* stream.go:362-377 threshold(rank), exact int64 truncation */
@@ -414,45 +444,49 @@ __device__ __forceinline__ int64_t ckms_threshold(const RollupPlan& plan,
     return min_val;
 }
 
-/* insert sorted batch (stream.go:280-331) + compress (:333-401); lane 0
- * does the sequential merge/walk, the wave sorts. `sorted` is dedicated LDS scratch. */
+/* insert the sorted bufMore (stream.go:280-331) + compress (:333-401);
+ * lane 0 does the heap sort and the sequential merge/walk. */
 __device__ void ckms_insert_compress(CkmsLds& L, CkmsState& st,
-                                     const RollupPlan& plan, double* sorted,
-                                     uint32_t lane) {
+                                     const RollupPlan& plan, uint32_t lane) {
     int32_t m = st.nmore;
-    ckms_sort(L.more, sorted, m, lane);
     if (st.len + m > CKMS_CAP) { /* uniform: all lanes see the same state */
         st.err = M3GPU_SERIES_BUCKET_OVERFLOW;
         return;
     }
     if (lane == 0) {
         int src = st.cur, dst = st.cur ^ 1;
-        int32_t n = st.len;
+        int32_t n = st.len; /* >= 1: the first value is always a sample */
         {
-            /* two-pointer merge == the reference's cursor walk */
-            int32_t i = 0, j = 0, o = 0;
+            /* :294-299 descending sort, consumed from the end */
+            double* vals = L.more;
+            ckms_heap_sort_desc(vals, m);
+            int32_t idx = m - 1;
+            /* two-pointer merge == the reference's cursor walk (:301-322) */
+            int32_t i = 0, o = 0;
             while (i < n) {
-                if (j < m && sorted[j] <= L.val[src][i]) {
-                    L.val[dst][o] = sorted[j];
+                double insert_point = L.val[src][i];
+                while (idx >= 0 && vals[idx] <= insert_point) {
+                    L.val[dst][o] = vals[idx];
                     L.nr[dst][o] = 1;
                     L.dl[dst][o] = L.nr[src][i] + L.dl[src][i] - 1;
-                    o++; j++;
-                } else {
-                    L.val[dst][o] = L.val[src][i];
-                    L.nr[dst][o] = L.nr[src][i];
-                    L.dl[dst][o] = L.dl[src][i];
-                    o++; i++;
+                    o++; idx--;
                 }
+                L.val[dst][o] = L.val[src][i];
+                L.nr[dst][o] = L.nr[src][i];
+                L.dl[dst][o] = L.dl[src][i];
+                o++; i++;
             }
-            while (j < m) { /* PushBack tail, delta 0 (:316-328) */
-                L.val[dst][o] = sorted[j];
+            /* PushBack while >= the current tail, delta 0 (:324-335); what
+             * fails the compare is dropped with everything behind it */
+            while (idx >= 0 && vals[idx] >= L.val[dst][o - 1]) {
+                L.val[dst][o] = vals[idx];
                 L.nr[dst][o] = 1;
                 L.dl[dst][o] = 0;
-                o++; j++;
+                o++; idx--;
             }
             st.cur = dst;
             st.len = o;
-            st.num_values += m;
+            st.num_values += o - n; /* numValues++ per inserted sample */
             /* compress (:333-401); entry cursor nil in this usage */
             int32_t len = st.len;
             if (len >= 3) {
@@ -506,7 +540,7 @@ __device__ void ckms_insert_compress(CkmsLds& L, CkmsState& st,
  * like Timer.AddBatch -> stream per-value adds in the rollup loop. */
 __device__ __forceinline__ void ckms_add(CkmsLds& L, CkmsState& st,
                                          const RollupPlan& plan, double v,
-                                         double* sorted, uint32_t lane) {
+                                         uint32_t lane) {
     if (st.err) return;
     if (st.len == 0 && st.nmore == 0 && st.nless == 0 && st.num_values == 0) {
         /* first value becomes the first sample (:88-97) */
@@ -526,17 +560,17 @@ __device__ __forceinline__ void ckms_add(CkmsLds& L, CkmsState& st,
         st.err = M3GPU_SERIES_BUCKET_OVERFLOW;
         return;
     }
-    if (v < insert_point) {
-        if (lane == 0) L.less[st.nless] = v;
+    if (v < insert_point) { /* a NaN goes to bufMore (:102-106) */
+        if (lane == 0) ckms_heap_push(L.less, st.nless, v);
         st.nless++;
     } else {
-        if (lane == 0) L.more[st.nmore] = v;
+        if (lane == 0) ckms_heap_push(L.more, st.nmore, v);
         st.nmore++;
     }
     __builtin_amdgcn_wave_barrier();
     __threadfence_block();
     if (st.counter == plan.every) { /* insertAndCompressEvery, checked BEFORE ++ */
-        ckms_insert_compress(L, st, plan, sorted, lane);
+        ckms_insert_compress(L, st, plan, lane);
         st.counter = 0;
     }
     st.counter++;
@@ -545,14 +579,14 @@ __device__ __forceinline__ void ckms_add(CkmsLds& L, CkmsState& st,
 /* stream.go:123-137 Flush */
 __device__ __forceinline__ void ckms_flush(CkmsLds& L, CkmsState& st,
                                            const RollupPlan& plan,
-                                           double* sorted, uint32_t lane) {
+                                           uint32_t lane) {
     while (!st.err && (st.nless > 0 || st.nmore > 0)) {
         if (st.nmore == 0) { /* resetInsertCursor: swap */
             double* t = L.less; L.less = L.more; L.more = t;
             st.nmore = st.nless;
             st.nless = 0;
         }
-        ckms_insert_compress(L, st, plan, sorted, lane);
+        ckms_insert_compress(L, st, plan, lane);
     }
 }
 
@@ -600,7 +634,7 @@ __device__ void ckms_calc_quantiles(const CkmsLds& L, const CkmsState& st,
 }
 
 /* ------------- the deep-bucket rollup kernel (third tier) -------------
- * One series per 64-thread workgroup (one wave), ~145 KB dynamic LDS
+ * One series per 64-thread workgroup (one wave), ~129 KB dynamic LDS
  * (CkmsLdsLayout) for the CKMS state. Only TIMER series with quantile aggs
  * can reach this tier (nothing else sets BUCKET_OVERFLOW). */
 __global__ void __launch_bounds__(CKMS_BLOCK)
@@ -629,7 +663,6 @@ k_rollup_ckms(const uint8_t* __restrict__ blobs,
     L.dl[1] = L.dl[0] + CKMS_CAP;
     L.less = (double*)(lds_raw + Lay::less);
     L.more = (double*)(lds_raw + Lay::more);
-    double* sorted = (double*)(lds_raw + Lay::sorted);
     double* computed = (double*)(lds_raw + Lay::computed);
     int64_t* thr_rank = (int64_t*)(lds_raw + Lay::thr_rank);
     int64_t* thr_thresh = (int64_t*)(lds_raw + Lay::thr_thresh);
@@ -650,7 +683,7 @@ k_rollup_ckms(const uint8_t* __restrict__ blobs,
 
     auto emit_bucket = [&](int64_t bk) {
         if (wts_row && lane == 0) wts_row[bk] = walk.window_end(bk, window_ns);
-        ckms_flush(L, st, plan, sorted, lane);
+        ckms_flush(L, st, plan, lane);
         if (st.err) return;
         if (lane == 0) {
             for (int i = 0; i < plan.nq; i++) computed[i] = 0.0;
@@ -695,7 +728,7 @@ k_rollup_ckms(const uint8_t* __restrict__ blobs,
             ckms_reset(st);
         }
         bucket_add<M3GPU_METRIC_TIMER>(bs, t, v);
-        ckms_add(L, st, plan, v, sorted, lane); /* one value at a time */
+        ckms_add(L, st, plan, v, lane); /* one value at a time */
         if (st.err) { err = st.err; break; }
     }
     if (lane == 0) out_errs[series] = err;

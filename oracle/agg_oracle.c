@@ -443,9 +443,16 @@ enum { METRIC_COUNTER = 0, METRIC_GAUGE = 1, METRIC_TIMER = 2 };
  *
  * Counter input values are int64 via Go conversion int64(value) of the f64
  * input (entry.go passes counter values as int64; our batch carries f64
- * storage of exact ints).
+ * storage). The conversion is defined for every f64: go_f2i below.
  */
 static double agg_quantile_of(int t);
+
+/* Go float64->int64 on amd64 (CVTTSD2SQ): truncation toward zero; NaN and
+ * values outside [-2^63, 2^63) give INT64_MIN. */
+static int64_t go_f2i(double v) {
+    if (!(v >= -9223372036854775808.0 && v < 9223372036854775808.0)) return INT64_MIN;
+    return (int64_t)v;
+}
 
 int oracle_rollup_series_opts(
     const int64_t* ts_ns, const double* vals, int64_t n,
@@ -503,12 +510,14 @@ int oracle_rollup_series_opts(
         int64_t t = ts_ns[i];
         switch (metric_type) {
         case METRIC_COUNTER: { /* counter.go:52-78 */
-            int64_t iv = (int64_t)v; /* in-range by contract */
-            bs->isum += iv;
+            int64_t iv = go_f2i(v);
+            /* Go's int64 sum and sumSq wrap: add and multiply in uint64_t */
+            bs->isum = (int64_t)((uint64_t)bs->isum + (uint64_t)iv);
             bs->count++;
             if (bs->imax < iv) bs->imax = iv;
             if (bs->imin > iv) bs->imin = iv;
-            bs->isumsq += iv * iv;
+            bs->isumsq = (int64_t)((uint64_t)bs->isumsq +
+                                   (uint64_t)iv * (uint64_t)iv);
             bs->any = 1;
             break;
         }
