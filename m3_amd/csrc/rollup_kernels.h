@@ -1,6 +1,6 @@
 /*
  * rollup_kernels.h — the fused decode->rollup kernels, all three tiers.
- * Device code: included once by m3tsz_kernels.hip, after the decoders.
+ * Device code, over the decoders of m3tsz_decoder.h.
  *
  *   k_rollup_lane<QMODE, METRIC>  one series per lane; every rollup starts here
  *   k_rollup_batch                one series per wave: timers whose quantile
@@ -28,6 +28,10 @@
 #ifndef M3_ROLLUP_KERNELS_H
 #define M3_ROLLUP_KERNELS_H
 
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "../../include/m3gpu.h"
+#include "m3tsz_decoder.h" /* Decoder, RingDecoder, RF_SPAN */
 #include "rollup_bucket.h"
 
 namespace m3 {

@@ -18,6 +18,7 @@
 
 /* shared by host code and kernels: host+device under hipcc, plain otherwise */
 #ifdef __HIPCC__
+#include <hip/hip_runtime.h> /* __forceinline__ */
 #define M3_HD __host__ __device__
 #define M3_INLINE __forceinline__
 #else
