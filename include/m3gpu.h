@@ -452,6 +452,103 @@ int m3gpu_decode_steps_batch(
     int64_t start_ns, int64_t step_ns, uint32_t nsteps, int64_t lookback_ns,
     double* out, uint32_t out_pitch, int32_t* out_errs);
 
+/* -------- batched temporal functions (replaces the temporal baseNode's
+ * per-series loop, query/functions/temporal/base.go:255-306 with getIndices,
+ * base.go:432-482, and the processors of aggregation.go, rate.go,
+ * functions.go and linear_regression.go): one range-vector function per
+ * (step, series), e.g. rate(x[5m]) for every series of a fetch. --------
+ *
+ * Rows are as for m3gpu_step_consolidate_batch_dev: d_ts, d_vals [nseries,
+ * stride], d_counts, and d_errs (NULL: every row is clean), what
+ * m3gpu_series_merge_batch_dev or a decode wrote. The output is the same
+ * step-major matrix, d_out[k*out_pitch + i]; exactly nsteps*nseries cells and
+ * d_out_errs[nseries] are written.
+ *
+ * Grid: t_k = start_ns + k*step_ns. The window W_k is the row's points, in
+ * row order, with t_k - range_ns <= ts <= t_k: BOTH ends inclusive, as
+ * getIndices has it (it skips ts < lBound and keeps ts <= rBound), not
+ * Prometheus' left-open window. NaN points are in the window; each function
+ * decides what to do with them. cell(k, i) = f(W_k), f the reference's
+ * processor operation for operation in its order, compiled without fused
+ * multiply-add:
+ *  - SUM, COUNT, AVG (sumAndCount, aggregation.go:236-251; :151-163,
+ *    :199-202): NaN skipped, left-to-right sum; no non-NaN point gives NaN.
+ *  - MIN, MAX (aggregation.go:165-197): Go's math.Min / math.Max over the
+ *    non-NaN values from +-Inf, so Min(0, -0) = -0 and Max(-0, 0) = +0.
+ *  - LAST (aggregation.go:227-234): the last point's value bit for bit, a NaN
+ *    and its payload included.
+ *  - STDVAR, STDDEV (aggregation.go:204-225): the Welford loop, one division
+ *    per non-NaN point; fewer than 2 gives NaN; STDDEV is its sqrt.
+ *  - RATE, INCREASE, DELTA (standardRateFunc, rate.go:150-240): fewer than 2
+ *    points, NaN ones counted, gives NaN; firstIdx / lastIdx are window
+ *    indices; durations are subSeconds, float64(a-b)/1e9; RATE alone divides
+ *    by time.Duration(range_ns).Seconds().
+ *  - IRATE, IDELTA (irateFunc, rate.go:242-298): the last two non-NaN points;
+ *    IRATE divides by Duration.Seconds() of their distance, which is
+ *    float64(d/1e9) + float64(d%1e9)/1e9 and not subSeconds.
+ *  - RESETS, CHANGES (functionNode.process, functions.go:89-118): prev starts
+ *    as the first point's value, NaN or not; an empty window, or only NaN
+ *    behind the first point, gives NaN.
+ *  - DERIV, PREDICT_LINEAR (linear_regression.go:127-191): fewer than 2
+ *    points, NaN ones counted, gives NaN; the intercept time is t_k for
+ *    PREDICT_LINEAR and the first non-NaN timestamp for DERIV; one non-NaN
+ *    value gives NaN, none falls through to 0/0. PREDICT_LINEAR returns
+ *    slope*param + intercept, param in seconds; other functions ignore param.
+ * Where the reference returns math.NaN() the cell holds 0x7FF8000000000001,
+ * as in the step matrix; sign and payload of a NaN that arithmetic produced
+ * are the hardware's.
+ *
+ * Errors: a batch keeps its other series. Series i fails when d_errs[i] is
+ * nonzero, wherever its points lie: the temporal node takes
+ * series.Datapoints(), the whole decoded series, before its first window.
+ * (m3gpu_step_consolidate_batch_dev differs: nextForStep meets a row's error
+ * only if it reads that far.) It fails with M3GPU_SERIES_OUT_OF_ORDER when,
+ * among the points from the row's first up to and including the first one
+ * past t_last, a timestamp is at or before its predecessor; nothing behind
+ * that point is read. A failed series' column is all 0x7FF8000000000001.
+ *
+ * Not built: quantile_over_time (a sort per window), holt_winters, a fused
+ * streams -> temporal entry, more than 4 replicas in the merge before it.
+ *
+ * M3GPU_ERR_BADARG, before any HIP call: step_ns <= 0; range_ns <= 0; nsteps
+ * 0; stride 0; out_pitch < nseries; fn outside the enum; start_ns +
+ * (nsteps-1)*step_ns or start_ns - range_ns outside int64. nseries 0
+ * succeeds and does nothing. */
+enum {  /* src/query/functions/temporal */
+    M3GPU_TEMPORAL_SUM, M3GPU_TEMPORAL_COUNT, M3GPU_TEMPORAL_AVG,
+    M3GPU_TEMPORAL_MIN, M3GPU_TEMPORAL_MAX, M3GPU_TEMPORAL_LAST,
+    M3GPU_TEMPORAL_STDDEV, M3GPU_TEMPORAL_STDVAR,          /* aggregation.go */
+    M3GPU_TEMPORAL_RATE, M3GPU_TEMPORAL_INCREASE, M3GPU_TEMPORAL_DELTA,
+    M3GPU_TEMPORAL_IRATE, M3GPU_TEMPORAL_IDELTA,           /* rate.go */
+    M3GPU_TEMPORAL_RESETS, M3GPU_TEMPORAL_CHANGES,         /* functions.go */
+    M3GPU_TEMPORAL_DERIV, M3GPU_TEMPORAL_PREDICT_LINEAR,   /* linear_regression.go */
+    M3GPU_TEMPORAL_FN_COUNT
+};
+
+int m3gpu_temporal_batch_dev(
+    const int64_t* d_ts, const double* d_vals, const uint32_t* d_counts,
+    const int32_t* d_errs,       /* NULL => every row is clean           */
+    uint32_t nseries, uint32_t stride,
+    int64_t start_ns, int64_t step_ns, uint32_t nsteps, int64_t range_ns,
+    int fn, double param,        /* predict_linear's seconds; else ignored */
+    double* d_out, uint32_t out_pitch, int32_t* d_out_errs,
+    void* hip_stream);
+
+/* host-pointer form (what a cgo temporal.baseNode replacement calls, base.go
+ * :227-321): upload, run on the null stream, copy back; blocks. out is
+ * [nsteps, out_pitch]; cells past nseries in a row are left alone. */
+int m3gpu_temporal_batch(
+    const int64_t* ts, const double* vals, const uint32_t* counts,
+    const int32_t* errs, uint32_t nseries, uint32_t stride,
+    int64_t start_ns, int64_t step_ns, uint32_t nsteps, int64_t range_ns,
+    int fn, double param,
+    double* out, uint32_t out_pitch, int32_t* out_errs);
+
+/* The depth C of the per-row LDS ring the library's temporal kernels were
+ * built with: windows of up to C points are read from LDS, longer ones reach
+ * into global memory for their older points. For tests and sizing. */
+int m3gpu_temporal_ring_depth(void);
+
 int m3gpu_rollup_batch(
     const uint8_t* blobs, uint64_t blobs_len,
     const uint64_t* offsets, const uint32_t* lens,

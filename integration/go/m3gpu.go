@@ -458,6 +458,117 @@ func DecodeStepsBatch(
 	return nil
 }
 
+// TemporalFn is one of the range-vector functions of
+// src/query/functions/temporal (M3GPU_TEMPORAL_* in m3gpu.h).
+type TemporalFn int32
+
+const (
+	TemporalSum TemporalFn = iota // aggregation.go
+	TemporalCount
+	TemporalAvg
+	TemporalMin
+	TemporalMax
+	TemporalLast
+	TemporalStdDev
+	TemporalStdVar
+	TemporalRate // rate.go
+	TemporalIncrease
+	TemporalDelta
+	TemporalIRate
+	TemporalIDelta
+	TemporalResets // functions.go
+	TemporalChanges
+	TemporalDeriv // linear_regression.go
+	TemporalPredictLinear
+)
+
+// TemporalOpTypes maps the temporal package's op types to TemporalFn.
+// quantile_over_time and holt_winters are not built and stay with Go.
+var TemporalOpTypes = map[string]TemporalFn{
+	"sum_over_time": TemporalSum, "count_over_time": TemporalCount,
+	"avg_over_time": TemporalAvg, "min_over_time": TemporalMin,
+	"max_over_time": TemporalMax, "last_over_time": TemporalLast,
+	"stddev_over_time": TemporalStdDev, "stdvar_over_time": TemporalStdVar,
+	"rate": TemporalRate, "increase": TemporalIncrease, "delta": TemporalDelta,
+	"irate": TemporalIRate, "idelta": TemporalIDelta,
+	"resets": TemporalResets, "changes": TemporalChanges,
+	"deriv": TemporalDeriv, "predict_linear": TemporalPredictLinear,
+}
+
+// TemporalBatch runs one temporal function for every series and step
+// (m3gpu_temporal_batch; query/functions/temporal/base.go:227-321 with
+// getIndices, base.go:432-482): what parallelProcess computes with one
+// processor per batch. ts and vals are rows of `stride` points, counts[i] of
+// them valid, rowErrs nil or one decode/merge error per series. The grid is
+// startNs + k*stepNs, k < nsteps; the window of a step is [t_k - rangeNs,
+// t_k], both ends inclusive as getIndices has them. param is
+// predict_linear's seconds. out is step-major, out[k*nseries + i], the
+// builder's columns; math.NaN() cells hold StepNaNBits. errs[i] != 0 (the
+// row's error, wherever its points lie, or 100 for a timestamp at or before
+// its predecessor) means series i's column is all NaN: fail the block as
+// iter.Err() would, or keep the other series.
+func TemporalBatch(
+	ts []int64, vals []float64, counts []uint32, rowErrs []SeriesError,
+	stride uint32, startNs, stepNs int64, nsteps uint32, rangeNs int64,
+	fn TemporalFn, param float64,
+) (out []float64, errs []SeriesError, err error) {
+	n := uint32(len(counts))
+	if n == 0 {
+		return nil, nil, nil
+	}
+	out = make([]float64, uint64(nsteps)*uint64(n))
+	errs = make([]SeriesError, n)
+	var rowErrsPtr *C.int32_t
+	if rowErrs != nil {
+		rowErrsPtr = (*C.int32_t)(unsafe.Pointer(&rowErrs[0]))
+	}
+	var outPtr *C.double
+	if len(out) > 0 {
+		outPtr = (*C.double)(unsafe.Pointer(&out[0]))
+	}
+	var tsPtr *C.int64_t
+	var valsPtr *C.double
+	if len(ts) > 0 {
+		tsPtr = (*C.int64_t)(unsafe.Pointer(&ts[0]))
+		valsPtr = (*C.double)(unsafe.Pointer(&vals[0]))
+	}
+	rc := C.m3gpu_temporal_batch(
+		tsPtr, valsPtr, (*C.uint32_t)(unsafe.Pointer(&counts[0])), rowErrsPtr,
+		C.uint32_t(n), C.uint32_t(stride), C.int64_t(startNs),
+		C.int64_t(stepNs), C.uint32_t(nsteps), C.int64_t(rangeNs), C.int(fn),
+		C.double(param), outPtr, C.uint32_t(n),
+		(*C.int32_t)(unsafe.Pointer(&errs[0])))
+	if rc != 0 {
+		return nil, nil, lastError()
+	}
+	return out, errs, nil
+}
+
+// TemporalBatchDev is TemporalBatch over DEVICE rows
+// (m3gpu_temporal_batch_dev): the rows SeriesMergeBatch or DecodeBatch's
+// device form wrote go in where they lie, dOut is [nsteps, outPitch] like
+// StepConsolidateBatch's. Enqueued on hipStream (nil: the null stream); the
+// caller synchronizes.
+func TemporalBatchDev(
+	dTs, dVals, dCounts, dErrs unsafe.Pointer,
+	nseries, stride uint32,
+	startNs, stepNs int64, nsteps uint32, rangeNs int64,
+	fn TemporalFn, param float64,
+	dOut unsafe.Pointer, outPitch uint32, dOutErrs unsafe.Pointer,
+	hipStream unsafe.Pointer,
+) error {
+	rc := C.m3gpu_temporal_batch_dev(
+		(*C.int64_t)(dTs), (*C.double)(dVals), (*C.uint32_t)(dCounts),
+		(*C.int32_t)(dErrs), C.uint32_t(nseries), C.uint32_t(stride),
+		C.int64_t(startNs), C.int64_t(stepNs), C.uint32_t(nsteps),
+		C.int64_t(rangeNs), C.int(fn), C.double(param), (*C.double)(dOut),
+		C.uint32_t(outPitch), (*C.int32_t)(dOutErrs), hipStream)
+	if rc != 0 {
+		return lastError()
+	}
+	return nil
+}
+
 // annRegionSize is the bytes one series' events need in an annotation
 // region: the event count, one 12-byte table entry per event, the bytes.
 func annRegionSize(evs []AnnotationEvent) uint64 {

@@ -44,6 +44,10 @@ from .engine import (  # noqa: F401
     decode_steps_dev,
     fetch_series_dev,
     fetch_steps_dev,
+    fetch_temporal_dev,
+    TEMPORAL_FNS,
+    temporal,
+    temporal_dev,
     lib,
     merge_batch_dev,
     series_merge,

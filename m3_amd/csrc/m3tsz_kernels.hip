@@ -41,6 +41,8 @@
  *                     k_regather, k_compact
  *   merge_kernels.h   k_merge<UNITS>, k_series_merge<UNITS>
  *   step_kernels.h    k_step_rows, k_step_fused
+ *   temporal_kernels.h k_temporal_rows<FAMILY, C>: the window functions of
+ *                     query/functions/temporal over the same rows and tile
  *   rollup_kernels.h  k_rollup_lane, k_rollup_batch, k_rollup_ckms, over
  *                     rollup_bucket.h (bucket walk, accumulate, ValueOf) and
  *                     rollup_plan.h (plan + exact-quantile index), both
@@ -60,6 +62,7 @@
 #include "encode_kernel.h"
 #include "merge_kernels.h"
 #include "step_kernels.h"
+#include "temporal_kernels.h"
 #include "rollup_kernels.h"
 
 /* ============================ C-ABI host layer ============================ */
@@ -652,6 +655,86 @@ int m3gpu_decode_steps_batch_dev(
     return M3GPU_OK;
 }
 
+/* argument rules of both temporal forms; touches no HIP state */
+static int temporal_check_args(uint32_t nseries, uint32_t stride,
+                               int64_t start_ns, int64_t step_ns,
+                               uint32_t nsteps, int64_t range_ns, int fn,
+                               uint32_t out_pitch) {
+    if (range_ns <= 0) {
+        snprintf(g_err, sizeof(g_err), "range_ns must be > 0");
+        return M3GPU_ERR_BADARG;
+    }
+    if (fn < 0 || fn >= M3GPU_TEMPORAL_FN_COUNT) {
+        snprintf(g_err, sizeof(g_err), "fn must be 0..%d",
+                 M3GPU_TEMPORAL_FN_COUNT - 1);
+        return M3GPU_ERR_BADARG;
+    }
+    int64_t lo;
+    if (__builtin_sub_overflow(start_ns, range_ns, &lo)) {
+        snprintf(g_err, sizeof(g_err), "start_ns - range_ns overflows int64");
+        return M3GPU_ERR_BADARG;
+    }
+    return step_check_args(nseries, stride, "stride", start_ns, step_ns,
+                           nsteps, range_ns, out_pitch);
+}
+
+/* the family whose accumulator fn uses */
+static int temporal_family(int fn) {
+    switch (fn) {
+    case M3GPU_TEMPORAL_MIN: case M3GPU_TEMPORAL_MAX: return m3::TF_MINMAX;
+    case M3GPU_TEMPORAL_STDDEV: case M3GPU_TEMPORAL_STDVAR:
+        return m3::TF_WELFORD;
+    case M3GPU_TEMPORAL_RATE: case M3GPU_TEMPORAL_INCREASE:
+    case M3GPU_TEMPORAL_DELTA: return m3::TF_RATE;
+    case M3GPU_TEMPORAL_IRATE: case M3GPU_TEMPORAL_IDELTA: return m3::TF_IRATE;
+    case M3GPU_TEMPORAL_RESETS: case M3GPU_TEMPORAL_CHANGES:
+        return m3::TF_CHANGES;
+    case M3GPU_TEMPORAL_DERIV: case M3GPU_TEMPORAL_PREDICT_LINEAR:
+        return m3::TF_REGR;
+    default: return m3::TF_SUM; /* sum, count, avg, last */
+    }
+}
+
+int m3gpu_temporal_batch_dev(
+    const int64_t* d_ts, const double* d_vals, const uint32_t* d_counts,
+    const int32_t* d_errs, uint32_t nseries, uint32_t stride,
+    int64_t start_ns, int64_t step_ns, uint32_t nsteps, int64_t range_ns,
+    int fn, double param, double* d_out, uint32_t out_pitch,
+    int32_t* d_out_errs, void* hip_stream) {
+    int rc = temporal_check_args(nseries, stride, start_ns, step_ns, nsteps,
+                                 range_ns, fn, out_pitch);
+    if (rc != M3GPU_OK) return rc;
+    if (!nseries) return M3GPU_OK;
+    const m3::StepGrid g = {start_ns, step_ns, range_ns, nsteps};
+    decltype(&m3::k_temporal_rows<m3::TF_SUM, TEMPORAL_RING>) kern;
+    switch (temporal_family(fn)) {
+    case m3::TF_MINMAX:
+        kern = m3::k_temporal_rows<m3::TF_MINMAX, TEMPORAL_RING>; break;
+    case m3::TF_WELFORD:
+        kern = m3::k_temporal_rows<m3::TF_WELFORD, TEMPORAL_RING>; break;
+    case m3::TF_RATE:
+        kern = m3::k_temporal_rows<m3::TF_RATE, TEMPORAL_RING>; break;
+    case m3::TF_IRATE:
+        kern = m3::k_temporal_rows<m3::TF_IRATE, TEMPORAL_RING>; break;
+    case m3::TF_CHANGES:
+        kern = m3::k_temporal_rows<m3::TF_CHANGES, TEMPORAL_RING>; break;
+    case m3::TF_REGR:
+        kern = m3::k_temporal_rows<m3::TF_REGR, TEMPORAL_RING>; break;
+    default:
+        kern = m3::k_temporal_rows<m3::TF_SUM, TEMPORAL_RING>; break;
+    }
+    hipLaunchKernelGGL(kern, dim3(grid_lane(nseries)), dim3(BLOCK_THREADS), 0,
+                       (hipStream_t)hip_stream,
+                       d_ts, d_vals, d_counts, d_errs, nseries, stride, g, fn,
+                       param, d_out, out_pitch, d_out_errs);
+    HIP_TRY(hipGetLastError());
+    return M3GPU_OK;
+}
+
+/* the ring depth this library was built with (TEMPORAL_RING), for tests that
+ * size their windows around it */
+int m3gpu_temporal_ring_depth(void) { return TEMPORAL_RING; }
+
 /* ---------- host-pointer convenience forms (the cgo surface) ---------- */
 
 /* the dense device matrix [nsteps, nseries] into out's rows of out_pitch:
@@ -691,6 +774,36 @@ int m3gpu_step_consolidate_batch(
     rc = m3gpu_step_consolidate_batch_dev(
         d_ts.p, d_vals.p, d_counts.p, d_errs.p, nseries, stride, start_ns,
         step_ns, nsteps, lookback_ns, d_out.p, nseries, d_out_errs.p, nullptr);
+    if (rc != M3GPU_OK) return rc;
+    return step_download(d_out, d_out_errs, nseries, nsteps, out, out_pitch,
+                         out_errs);
+}
+
+int m3gpu_temporal_batch(
+    const int64_t* ts, const double* vals, const uint32_t* counts,
+    const int32_t* errs, uint32_t nseries, uint32_t stride,
+    int64_t start_ns, int64_t step_ns, uint32_t nsteps, int64_t range_ns,
+    int fn, double param, double* out, uint32_t out_pitch,
+    int32_t* out_errs) {
+    int rc = temporal_check_args(nseries, stride, start_ns, step_ns, nsteps,
+                                 range_ns, fn, out_pitch);
+    if (rc != M3GPU_OK) return rc;
+    if (!nseries) return M3GPU_OK;
+    DevBuf<int64_t> d_ts;
+    DevBuf<double> d_vals, d_out;
+    DevBuf<uint32_t> d_counts;
+    DevBuf<int32_t> d_errs, d_out_errs;
+    const uint64_t npts = (uint64_t)nseries * stride;
+    HIP_TRY(d_ts.upload(ts, npts));
+    HIP_TRY(d_vals.upload(vals, npts));
+    HIP_TRY(d_counts.upload(counts, nseries));
+    if (errs) HIP_TRY(d_errs.upload(errs, nseries));
+    HIP_TRY(d_out.alloc((uint64_t)nsteps * nseries));
+    HIP_TRY(d_out_errs.alloc(nseries));
+    rc = m3gpu_temporal_batch_dev(
+        d_ts.p, d_vals.p, d_counts.p, d_errs.p, nseries, stride, start_ns,
+        step_ns, nsteps, range_ns, fn, param, d_out.p, nseries, d_out_errs.p,
+        nullptr);
     if (rc != M3GPU_OK) return rc;
     return step_download(d_out, d_out_errs, nseries, nsteps, out, out_pitch,
                          out_errs);

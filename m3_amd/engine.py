@@ -123,6 +123,18 @@ def lib():
                                                c_u8, c_i64, c_i64, c_u32,
                                                c_i64, P(c_f64), c_u32,
                                                P(c_i32)]
+        L.m3gpu_temporal_batch_dev.restype = c_int
+        L.m3gpu_temporal_batch_dev.argtypes = [c_vp, c_vp, c_vp, c_vp, c_u32,
+                                               c_u32, c_i64, c_i64, c_u32,
+                                               c_i64, c_int, c_f64, c_vp,
+                                               c_u32, c_vp, c_vp]
+        L.m3gpu_temporal_batch.restype = c_int
+        L.m3gpu_temporal_batch.argtypes = [P(c_i64), P(c_f64), P(c_u32),
+                                           P(c_i32), c_u32, c_u32, c_i64,
+                                           c_i64, c_u32, c_i64, c_int, c_f64,
+                                           P(c_f64), c_u32, P(c_i32)]
+        L.m3gpu_temporal_ring_depth.restype = c_int
+        L.m3gpu_temporal_ring_depth.argtypes = []
         L.m3gpu_decode_batch.restype = c_int
         L.m3gpu_decode_batch.argtypes = [P(c_u8), c_u64, P(c_u64), P(c_u32), c_u32,
                                          c_int, c_u8, P(c_i64), P(c_f64), P(c_u32),
@@ -872,6 +884,117 @@ def fetch_steps_dev(torch, d_blob, d_offsets, d_lens, nreplicas, nblocks,
     step_consolidate_dev(m_ts, m_vals, m_counts, start_ns, step_ns, nsteps,
                          lookback_ns, out["steps"], out["errs"],
                          d_errs=m_errs)
+    return out
+
+
+# PromQL names of the temporal functions -> M3GPU_TEMPORAL_* (m3gpu.h)
+TEMPORAL_FNS = dict(
+    sum_over_time=0, count_over_time=1, avg_over_time=2, min_over_time=3,
+    max_over_time=4, last_over_time=5, stddev_over_time=6, stdvar_over_time=7,
+    rate=8, increase=9, delta=10, irate=11, idelta=12, resets=13, changes=14,
+    deriv=15, predict_linear=16)
+
+
+def _temporal_fn(fn):
+    if isinstance(fn, str):
+        if fn not in TEMPORAL_FNS:
+            raise M3GpuError(f"unknown temporal function {fn!r}; one of "
+                             f"{sorted(TEMPORAL_FNS)}")
+        return TEMPORAL_FNS[fn]
+    return int(fn)
+
+
+def temporal_dev(d_ts, d_vals, d_counts, start_ns, step_ns, nsteps, range_ns,
+                 fn, out, out_errs, d_errs=None, param=0.0):
+    """Batched temporal function over rows (m3gpu_temporal_batch_dev): for
+    every series and every step t_k = start_ns + k*step_ns, `fn` (a
+    TEMPORAL_FNS name or its id) over the row's points with t_k - range_ns <=
+    ts <= t_k, both ends inclusive. Rows, out and out_errs are as in
+    step_consolidate_dev; a nonzero d_errs entry fails its series wherever
+    its points lie. `param` is predict_linear's seconds. Enqueues on the
+    current stream."""
+    nseries = d_counts.numel()
+    rc = lib().m3gpu_temporal_batch_dev(
+        _dev_ptr(d_ts), _dev_ptr(d_vals), _dev_ptr(d_counts),
+        _dev_ptr(d_errs) if d_errs is not None else None, nseries,
+        d_ts.shape[-1], start_ns, step_ns, nsteps, range_ns,
+        _temporal_fn(fn), float(param), _dev_ptr(out),
+        out.stride(0) if out.dim() == 2 else nseries, _dev_ptr(out_errs),
+        _torch_stream())
+    _check(rc, "m3gpu_temporal_batch_dev")
+
+
+def temporal(ts, vals, counts, start_ns, step_ns, nsteps, range_ns, fn,
+             errs=None, param=0.0):
+    """Host form of temporal_dev over numpy arrays; blocks. Returns (matrix
+    float64 [nsteps, nseries], errs int32 [nseries])."""
+    ts = _np(ts, np.int64)
+    vals = _np(vals, np.float64)
+    counts = _np(counts, np.uint32)
+    if errs is not None:
+        errs = _np(errs, np.int32)
+    nseries = counts.size
+    stride = ts.shape[-1] if ts.ndim == 2 else 0
+    out = np.zeros((nsteps, nseries), dtype=np.float64)
+    out_errs = np.zeros(nseries, dtype=np.int32)
+    rc = lib().m3gpu_temporal_batch(
+        _pp(ts, c_i64), _pp(vals, c_f64), _pp(counts, c_u32),
+        _pp(errs, c_i32) if errs is not None else None, nseries, stride,
+        start_ns, step_ns, nsteps, range_ns, _temporal_fn(fn), float(param),
+        _pp(out, c_f64), nseries, _pp(out_errs, c_i32))
+    _check(rc, "m3gpu_temporal_batch")
+    return out, out_errs
+
+
+def fetch_temporal_dev(torch, d_blob, d_offsets, d_lens, nreplicas, nblocks,
+                       stride, start_ns, step_ns, nsteps, range_ns, fn,
+                       param=0.0, strategy=EQUAL_TS_LAST_PUSHED,
+                       int_optimized=True, default_unit=1):
+    """A range-vector function over a fetch of nblocks blocks x nreplicas
+    replicas per series, e.g. rate(x[5m]): decode, series merge (no range
+    filter), temporal_dev. One replica of one block is its own series
+    iterator, so the merge is skipped and the decoded rows go straight in.
+    A zero-length stream is an absent block, exactly as in fetch_steps_dev.
+    Streams are packed as for fetch_series_dev. Returns a dict of device
+    tensors: steps float64 [nsteps, nseries] and errs int32 [nseries], what
+    iterators.StepIter walks. Enqueues on the current stream; the caller
+    synchronizes."""
+    nrows = d_lens.numel()
+    nseries = nrows // (nreplicas * nblocks)
+    if nseries * nreplicas * nblocks != nrows:
+        raise M3GpuError(
+            f"{nrows} streams are not {nreplicas} replicas x {nblocks} blocks "
+            f"of a whole number of series")
+    dev = d_blob.device
+    out = dict(
+        steps=torch.empty((nsteps, nseries), dtype=torch.float64, device=dev),
+        errs=torch.empty(nseries, dtype=torch.int32, device=dev))
+    if nreplicas * nblocks == 1:
+        stride = (stride + 1) & ~1  # even: two points a load
+    r_ts = torch.empty((nrows, stride), dtype=torch.int64, device=dev)
+    r_vals = torch.empty((nrows, stride), dtype=torch.float64, device=dev)
+    r_counts = torch.empty(nrows, dtype=torch.int32, device=dev)
+    r_errs = torch.empty(nrows, dtype=torch.int32, device=dev)
+    decode_batch_dev(d_blob, d_offsets, d_lens, r_ts, r_vals, r_counts,
+                     r_errs, int_optimized=int_optimized,
+                     default_unit=default_unit)
+    # an absent block is no reader at all, not one that fails with EOF
+    r_errs.masked_fill_(d_lens == 0, 0)
+    if nreplicas * nblocks == 1:
+        temporal_dev(r_ts, r_vals, r_counts, start_ns, step_ns, nsteps,
+                     range_ns, fn, out["steps"], out["errs"], d_errs=r_errs,
+                     param=param)
+        return out
+    out_stride = (nblocks * stride + 1) & ~1
+    m_ts = torch.empty((nseries, out_stride), dtype=torch.int64, device=dev)
+    m_vals = torch.empty((nseries, out_stride), dtype=torch.float64,
+                         device=dev)
+    m_counts = torch.empty(nseries, dtype=torch.int32, device=dev)
+    m_errs = torch.empty(nseries, dtype=torch.int32, device=dev)
+    series_merge_dev(r_ts, r_vals, r_counts, nreplicas, nblocks, m_ts, m_vals,
+                     m_counts, m_errs, d_errs=r_errs, strategy=strategy)
+    temporal_dev(m_ts, m_vals, m_counts, start_ns, step_ns, nsteps, range_ns,
+                 fn, out["steps"], out["errs"], d_errs=m_errs, param=param)
     return out
 
 

@@ -228,7 +228,12 @@ class StepIter:
     156-158,191-194) one series' error fails the block: Next() is false from
     the start and Err() names the first failed series. The matrix keeps the
     other series' columns; series_errors=False walks them, the failed
-    series' columns being all NaN."""
+    series' columns being all NaN.
+    The matrix of m3gpu_temporal_batch_dev (engine.temporal_dev, temporal,
+    fetch_temporal_dev) has the same shape, NaN pattern and errs, and is
+    walked unchanged: Current() is then the temporal function's column for
+    that step, what the temporal node's builder hands on (temporal/base.go:
+    289-306)."""
 
     def __init__(self, steps, errs, start_ns, step_ns, series_errors=True):
         self._steps = np.asarray(steps)
